@@ -13,10 +13,17 @@ Workload (BASELINE.json configs[1]): unet.UNet(n_channels=1, n_classes=2), 256x2
 multiclass Dice (the n_classes=2 form of train_end2end_jsrt.py:181-183).  Data parallel: RCCL all-reduce
 (average) of the 31 M gradients, bucketed and overlapped with backward.
 
-One JSON line on rank 0.  `roofline` is for the dominant MFMA kernel, measured live with HIP events on the
-launch stream inside the timed region: achieved = algorithmic FLOPs (2*M*N*K of the convolutions it ran)
-/ its summed launch time.  `cpu_baseline` is the CPU oracle (a port, oracle/oracle.py) timed on the host
-cores of this box on a bounded sample (batch 4), N=1 only.
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline figures
+(`value`, `ms_per_step`, ...); everything else is measured only with --full (null in a plain run):
+`roofline` and `kernels` are for the MFMA kernels, measured live with HIP events on the launch stream inside
+the timed region: achieved = algorithmic FLOPs (2*M*N*K of the convolutions it ran) / its summed launch time.
+`fast_mode` is a second timed leg in the fast 16-bit mode (N=1).  `cpu_baseline` is the CPU oracle (a port,
+oracle/oracle.py) timed on the host cores of this box on a bounded sample (batch 4), N=1 only.  N>1 adds the
+un-overlapped all-reduce time and a leg without the gradient exchange.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0): logits.npy, loss.npy and one
+grad.<parameter>.npy per parameter (float32, the loss float64; logits above DUMP_MAX_LOGITS and gradients above
+DUMP_MAX_ELEMS elements as a fixed seeded sample; DUMP_MAX_BYTES in all).
 """
 import argparse
 import json
@@ -44,6 +51,9 @@ GF_PER_IMG_FWDBWD = {1: 288.48, 2: 288.50}     # conv/convT 2*MA
 MFMA_PEAK_TFLOPS = 2500.0                      # dense bf16/fp16, MI355X_MICROARCH.md
 MFMA_SUSTAINED_TFLOPS = 1560.0                 # tools/mfma_peak.hip on this part: 32x32x16 f16, random operands
 HBM_PEAK_GBS = 8000.0
+DUMP_MAX_ELEMS = 1 << 18                       # per dumped gradient: 1 MiB of float32 (the U-Net's 64 gradients: 19 MiB)
+DUMP_MAX_LOGITS = 1 << 23                      # dumped logits: 32 MiB of float32 (the default 32x2x256x256 are written whole)
+DUMP_MAX_BYTES = 64 << 20
 
 
 # KernelTimer class -> kernel-name prefix in the committed rocprofv3 PMC summary (tools/profile_step.sh)
@@ -139,10 +149,16 @@ def parse():
                     help="numerics mode of the headline leg (`value`, `ms_per_step`, `roofline`, `kernels`).  Default 'mixed': what "
                          "UNet() builds and the mode whose asserted bound meets the north star's 1e-3 on logits; 'full': three MFMA "
                          "segments everywhere (~1e-5); 'fast': single 16-bit storage (~4e-3, outside the tolerance)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: per-kernel table and roofline (HIP events around the kernels of "
+                         "the timed steps), the fast_mode leg, the CPU baseline, and at N>1 the un-overlapped all-reduce and a leg "
+                         "without the gradient exchange")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (logits, loss, parameter gradients) as DIR/<name>.npy")
     ap.add_argument("--fast-leg", default="fast", choices=["fast", "none"],
-                    help="second timed leg at N=1 in the fast 16-bit mode, reported as \"fast_mode\" with its own (out-of-tolerance) "
-                         "bound next to the headline value (none: skip it, e.g. under rocprofv3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: second timed leg at N=1 in the fast 16-bit mode, reported as \"fast_mode\" with its own "
+                         "(out-of-tolerance) bound next to the headline value (none: skip it, e.g. under rocprofv3)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--global-dice", action="store_true",
                     help="exact global-batch Dice across ranks (all-reduce of three scalars); default: per-rank Dice")
     ap.add_argument("--host-input", action="store_true",
@@ -190,6 +206,33 @@ def cpu_baseline(args):
             "sample": f"oracle.unet_step fp32, UNet(1,{args.classes}) {args.size}x{args.size} batch {args.cpu_batch}, "
                       f"{args.cpu_steps} timed steps after 1 warm-up, torch {torch.__version__} CPU",
             "gflops": round(ips * GF_PER_IMG_FWDBWD.get(args.classes, 288.5) * (args.size / 256.0) ** 2, 1)}
+
+
+def dump_sample(t, n, seed):
+    """t as float32 numpy; with more than n elements, the same n of its flattened values in every run (sorted indices drawn from
+    a fixed seed), so that two builds compare element for element."""
+    import numpy as np
+    t = t.detach()
+    if t.numel() > n:
+        idx = np.sort(np.random.default_rng(seed).choice(t.numel(), n, replace=False))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, logits, loss, net):
+    """What a caller of the timed step receives, as .npy files: the logits and every parameter's gradient, flattened (float32,
+    sampled above DUMP_MAX_LOGITS / DUMP_MAX_ELEMS elements), and the loss (float64)."""
+    import numpy as np
+    arrays = {"logits": dump_sample(logits, DUMP_MAX_LOGITS, 0),
+              "loss": np.asarray(loss.detach().double().item(), dtype=np.float64)}
+    for i, (name, p) in enumerate(net.named_parameters()):
+        arrays[f"grad.{name}"] = dump_sample(p.grad.reshape(-1), DUMP_MAX_ELEMS, 1 + i)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def free_port() -> int:
@@ -339,7 +382,8 @@ def main():
 
     def timed_leg(precise, with_reducer):
         """W warm-up steps, then exactly K timed steps of forward + loss + backward in the given numerics mode, bracketed by a
-        barrier + synchronize on both sides; returns (elapsed seconds, per-step ms, per-kernel summary, last loss, reducer)."""
+        barrier + synchronize on both sides; returns (elapsed seconds, per-step ms, per-kernel summary (None without --full),
+        last logits, last loss, reducer, net)."""
         torch.manual_seed(1234)
         net = UNet(1, args.classes, compute_dtype=args.dtype, precise={"full": True, "mixed": "mixed", "fast": False}[precise]).to(dev)
         net.train()
@@ -355,15 +399,19 @@ def main():
             xs, ms_ = x, mask
             if args.host_input:
                 xs, ms_ = x_host.to(dev, non_blocking=True), mask_host.to(dev, non_blocking=True)
-            loss = seg_loss(net(xs), ms_, global_dice=True if (args.global_dice and multi) else None)
+            logits = net(xs)
+            loss = seg_loss(logits, ms_, global_dice=True if (args.global_dice and multi) else None)
             loss.backward()
-            return loss
+            return logits, loss
 
-        probe = ops.KernelTimer()                  # one untimed step counts the bracketed launches ...
+        # one untimed step first (with --full it counts the bracketed launches, so every event exists beforehand)
+        probe = ops.KernelTimer() if args.full else None
         ops.TIMER = probe
         step()
         ops.TIMER = None
-        timer = ops.KernelTimer(pool=2 * len(probe.records) * (args.steps + args.warmup) + 64)      # ... so every event exists beforehand
+        timer = None
+        if args.full:
+            timer = ops.KernelTimer(pool=2 * len(probe.records) * (args.steps + args.warmup) + 64)
         # the W warm-up steps come AFTER the event pool is built (thousands of hipEventCreate calls: milliseconds of idle GPU) and
         # run with the timer attached, so the timed region starts from the steady state it measures (the first timed step used to
         # read 14.0 ms against 12.3 for the other nineteen: clocks ramping back up)
@@ -371,7 +419,8 @@ def main():
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
-        timer.reset()
+        if timer is not None:
+            timer.reset()
         if multi:
             dist.barrier()
         torch.cuda.synchronize()
@@ -379,7 +428,7 @@ def main():
         t0 = time.perf_counter()
         marks[0].record()
         for i in range(args.steps):
-            loss = step()
+            logits, loss = step()
             marks[i + 1].record()
         if multi:
             dist.barrier()
@@ -387,14 +436,17 @@ def main():
         elapsed = time.perf_counter() - t0
         ops.TIMER = None
         step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
-        return elapsed, step_ms, timer.summary(), loss, reducer
+        return elapsed, step_ms, None if timer is None else timer.summary(), logits, loss, reducer, net
 
-    elapsed, step_ms, ksum, loss, reducer = timed_leg(args.precise, True)
+    elapsed, step_ms, ksum, logits, loss, reducer, net = timed_leg(args.precise, True)
     if os.environ.get("GSSEG_BENCH_VERBOSE"):
         sys.stderr.write("step ms: " + " ".join(f"{v:.2f}" for v in step_ms) + "\n")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, logits, loss, net)
+    del logits, net
     # the gradient exchange on its own (not overlapped with anything), for the scaling discussion: all buckets back to back
     allreduce_ms = None
-    if reducer is not None:
+    if args.full and reducer is not None:
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         reps = 5
@@ -415,15 +467,15 @@ def main():
     # barrier + max-over-ranks timing: ms_per_step - ms_per_step_no_exchange = what the exchange costs after overlap ("exposed"),
     # next to `allreduce_ms_per_step_unoverlapped` (all buckets back to back with nothing to hide behind)
     no_exchange_ms = None
-    if multi:
-        ne_elapsed, _, _, _, _ = timed_leg(args.precise, False)
+    if args.full and multi:
+        ne_elapsed = timed_leg(args.precise, False)[0]
         t = torch.tensor([ne_elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         no_exchange_ms = float(t.item()) / args.steps * 1e3
     # second leg, N = 1 only (like the CPU baseline): the fast 16-bit mode, whose logits are OUTSIDE the north star's tolerance
     fast = None
-    if world == 1 and not multi and args.fast_leg != "none" and args.precise == "mixed":
-        p_elapsed, p_step_ms, p_ksum, p_loss, _ = timed_leg("fast", False)
+    if args.full and world == 1 and not multi and args.fast_leg != "none" and args.precise == "mixed":
+        p_elapsed, p_step_ms, p_ksum, _, p_loss, _, _ = timed_leg("fast", False)
         fast = {"mode": PARITY_MODES["fast"][0], "value": round(args.batch * args.steps / p_elapsed, 2),
                 "unit": "images/sec", "ms_per_step": round(p_elapsed / args.steps * 1e3, 3),
                 "ms_per_step_median": round(statistics.median(p_step_ms), 3),
@@ -439,7 +491,7 @@ def main():
     ms = elapsed / args.steps * 1e3
     value = world * args.batch * args.steps / elapsed
     gf = GF_PER_IMG_FWDBWD.get(args.classes, 288.5) * (args.size / 256.0) ** 2
-    kern = kernel_table(ksum, args.steps)
+    kern = kernel_table(ksum, args.steps) if args.full else None
     # the dominant kernel FAMILY (sub-entries "x.y" are parts of family "x" and are not candidates)
     dom = max((k for k in kern if "." not in k), key=lambda k: kern[k]["ms_per_step"]) if kern else None
     roof = None
@@ -477,9 +529,9 @@ def main():
         "exposed_exchange_ms_per_step": None if no_exchange_ms is None else round(ms - no_exchange_ms, 3),
         "whole_step_tflops": round(value * gf / 1e3, 1),
         "whole_step_frac_of_mfma_peak": round(value * gf / 1e3 / (MFMA_PEAK_TFLOPS * world), 4),
-        "roofline": roof, "kernels": kern,
+        "roofline": roof, "kernels": kern, "full": args.full,
     }
-    if world == 1 and not multi and not args.no_cpu_baseline:
+    if args.full and world == 1 and not multi and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     else:
         out["cpu_baseline"] = None

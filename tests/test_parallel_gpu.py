@@ -239,13 +239,14 @@ def test_unet3d_and_pix2pix_steps_replayed_from_hipgraphs_then_exchanged_over_rc
 def test_bench_data_parallel_path_rehearsal_on_one_rank():
     """`bench.py --rehearse-dp`: the code path of `bench.py --gpus N` (N > 1) on ONE rank -- a 1-rank RCCL process group, the timed leg
     with the bucketed GradReducer attached, the back-to-back bucket all-reduce, the timed leg with the reducer detached -- so that
-    the path the driver's scaling run executes has run on a GPU before.  (A subprocess: bench.py owns its process group.)"""
+    the path a multi-GPU scaling run executes has run on a GPU before.  --full: the un-overlapped all-reduce and the detached leg are
+    measured only there.  (A subprocess: bench.py owns its process group.)"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rehearse-dp", "--steps", "2", "--warmup", "1", "--batch", "4",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rehearse-dp", "--full", "--steps", "2", "--warmup", "1", "--batch", "4",
                         "--size", "128"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -254,3 +255,55 @@ def test_bench_data_parallel_path_rehearsal_on_one_rank():
     assert d["grad_buckets"] >= 1 and d["allreduce_ms_per_step_unoverlapped"] > 0
     assert d["ms_per_step_no_exchange"] > 0 and d["exposed_exchange_ms_per_step"] is not None
     assert d["meets_north_star_tolerance"] is True and d["value"] > 0
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and measures nothing else (the --full figures are null); with
+    --dump-outputs it writes the last timed step's logits, loss and parameter gradients.  The dumped logits give the reported
+    loss and the head bias gradient of that loss; runs with other step counts dump the same values (same inputs, same
+    weights, same sampled gradient elements); logits above bench.DUMP_MAX_LOGITS are sampled within the 64 MiB budget."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    from oracle import oracle
+    from semantic_segmentation_amd.harness import synthetic_batch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+
+    def bench(out, *args):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", *args, "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        return d, {f.name[:-4]: np.load(f) for f in out.glob("*.npy")}
+
+    d, a = bench(tmp_path / "a", "--steps", "3", "--warmup", "1", "--batch", "2", "--size", "64")
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f16"
+    assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) <= 1e-2 * d["value"]
+    assert d["full"] is False
+    assert all(d[k] is None for k in ("kernels", "roofline", "fast_mode", "cpu_baseline"))
+    logits, loss = a["logits"], a["loss"]
+    assert logits.dtype == np.float32 and logits.shape == (2, 2, 64, 64) and np.isfinite(logits).all()
+    assert loss.dtype == np.float64 and loss.shape == () and float(loss) == d["config"]["loss"]
+    grads = {k: v for k, v in a.items() if k.startswith("grad.")}
+    assert len(grads) == 64                                  # every parameter of UNet(1, 2)
+    for g in grads.values():
+        assert g.dtype == np.float32 and g.ndim == 1 and 0 < g.size <= 1 << 18 and np.isfinite(g).all()
+    # the logits, the loss and the gradients belong to one step
+    mask = synthetic_batch(2, 64, seed=1234)[1]
+    lt = torch.from_numpy(logits).double().requires_grad_(True)
+    ref = oracle.seg_loss(lt, mask)
+    ref.backward()
+    assert abs(float(ref.detach()) - float(loss)) <= 1e-5 * abs(float(ref.detach()))
+    np.testing.assert_allclose(grads["grad.outc.conv.bias"], lt.grad.sum((0, 2, 3)).numpy(), rtol=1e-3, atol=1e-6)
+    # the same inputs, weights and sampled elements in another run
+    _, b = bench(tmp_path / "b", "--steps", "1", "--warmup", "0", "--batch", "2", "--size", "64")
+    assert sorted(b) == sorted(a)
+    for k in a:
+        np.testing.assert_allclose(b[k], a[k], rtol=1e-5, atol=1e-6 * float(np.abs(a[k]).max()), err_msg=k)
+    # logits above the cap: a fixed sample, the whole dump within its budget
+    _, c = bench(tmp_path / "c", "--steps", "1", "--warmup", "0", "--batch", "17", "--size", "512")
+    assert c["logits"].shape == (1 << 23,) and np.isfinite(c["logits"]).all()
+    assert sum(v.nbytes for v in c.values()) <= 64 << 20
