@@ -204,6 +204,9 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
+    # torch first: its wheel carries its own HIP runtime, and this library must bind to the SAME one.  Loaded before torch (build()
+    # followed by smoke() in one process), it binds to the system's copy and its launches fail with "no ROCm-capable device".
+    import torch  # noqa: F401
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(
             f"{LIB_PATH} not found: the HIP extension is not built.  Run "

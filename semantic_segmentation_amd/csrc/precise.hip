@@ -805,6 +805,8 @@ extern "C" int gs_bn_act_apply_split_pool3d(const void* y_hi, const void* y_lo, 
     GS_CHECK_ARG(act == GS_ACT_NONE || act == GS_ACT_RELU || act == GS_ACT_LEAKY02, "gs_bn_act_apply_split_pool3d: activation %d", act);
     GS_CHECK_ARG(dtype == GS_F16 || dtype == GS_BF16, "gs_bn_act_apply_split_pool3d: bad dtype");
     GS_CHECK_ARG((int64_t)NB * D * H * W < 2147483000LL, "gs_bn_act_apply_split_pool3d: too many voxels");
+    GS_CHECK_ARG(((uintptr_t)y_hi | (uintptr_t)y_lo | (uintptr_t)z_hi | (uintptr_t)z_lo | (uintptr_t)zp_hi | (uintptr_t)zp_lo) % 16 == 0,
+                 "gs_bn_act_apply_split_pool3d: planes must be 16-byte aligned");
     ApplySArgs a{(const unsigned short*)y_hi, (const unsigned short*)y_lo, scale, shift, (unsigned short*)z_hi, (unsigned short*)z_lo,
                  (unsigned short*)zp_hi, (unsigned short*)zp_lo, act, NB * D, H, W, C, z_pix_stride, z_coff, zp_pix_stride};
     const int nch = C / 8;

@@ -1248,7 +1248,7 @@ def upconv2x2_fwd_precise(x, w, bias, y_hi, y_lo, N, IH, IW, Cin, Cout, OH, OW, 
               dt_code(x), _stream())
     if ev is not None:
         TIMER.stop("igemm_fwd_precise", ev, 2.0 * N * IH * IW * Cin * 4 * Cout,
-                   2.0 * (N * IH * IW * 2 * (Cin + 4 * Cout) + 4 * K * Cout))
+                   2.0 * (N * IH * IW * 2 * (Cin + 4 * Cout) + 4 * 3 * Cin * Cout))
 
 
 def pack_weight_segs(items):

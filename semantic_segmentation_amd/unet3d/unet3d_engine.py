@@ -74,7 +74,9 @@ def segs3d(mode: str, cin: int, lo0: int = 0, lo_len=None):
     plane (cin channels) followed by a lo plane of which the first lo_len channels are valid and belong to the layer's input
     channels [lo0, lo0 + lo_len) (a concat buffer stores [up_h res_h | res_l ...]: lo0 = the up channels, lo_len = the residual
     ones; a plain pair: lo0 = 0, lo_len = cin).  Kinds: 0 = hi(w), 1 = lo(w), 2 = zeros (pads K / the wrap to multiples of 64: the
-    padded K chunk multiplies channels of the lo plane by zero, which therefore must hold finite values)."""
+    padded K chunk multiplies channels of the lo plane by zero, which therefore must hold finite values: 0 * NaN = NaN.  Only
+    the first lo_len lo channels are ever written -- the buffers come from torch.empty -- so a zero segment is laid over those
+    alone; a layout that would need one behind them raises NotImplementedError and "auto" runs the 16-bit engine)."""
     ll = cin if lo_len is None else lo_len
     segs = [(0, 0, cin)]
     span = cin                                   # input channels the K extent walks before it wraps
@@ -83,7 +85,7 @@ def segs3d(mode: str, cin: int, lo0: int = 0, lo_len=None):
         span += ll
     if span % 64:
         pad = 64 - span % 64
-        if pad > ll:
+        if pad > ll or "x" in mode:               # "x": the walk already covers the valid lo channels, the pad would lie behind them
             raise NotImplementedError(f"pair forward: cannot pad a {cin}-channel input to a multiple of 64 channels")
         segs.append((2, 0, pad))
         span += pad
@@ -472,7 +474,7 @@ class UNet3DEngine:
             cup[k] = s_blocks[k].upconv1.out_channels
             cres = a_blocks[k - 1].conv2.out_channels
             D, H, W = dims[k - 1]
-            # the unused tail of the lo plane (the up channels) is never read: a consumer's x_lo / zero segments stop at cres
+            # the unused tail of the lo plane (the up channels) is never read: a consumer's x_lo / zero segments stop at cres (segs3d)
             cats[k] = empty(NB * D, H, W, 2 * (cup[k] + cres))
 
         # ---- analysis path ----

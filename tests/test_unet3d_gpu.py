@@ -185,6 +185,68 @@ def test_unet3d_multi_channel_input_vs_oracle(cin, ncls):
     assert float(np.median(list(errs.values()))) < 0.15 and max(errs.values()) < 0.3, errs
 
 
+def _poison_allocator():
+    """make the next torch.empty hand out NaN bit patterns: blocks larger than the network's activations, and a run of small ones
+    for the allocator's small pool, filled with NaN and freed"""
+    big = torch.full((96 << 20,), float("nan"), dtype=torch.float16, device="cuda")
+    small = [torch.full((n,), float("nan"), dtype=torch.float16, device="cuda") for n in (256, 4096, 65536, 262144) for _ in range(24)]
+    torch.cuda.synchronize()
+    del big, small
+
+
+def _narrow_run(levels, bott, precise, seed):
+    from semantic_segmentation_amd.unet3d import UNet3D
+    sd = oracle.unet3d_state_dict(1, 2, seed=seed, level_channels=levels, bottleneck_channel=bott)
+    net = UNet3D(1, 2, level_channels=levels, bottleneck_channel=bott, precise=precise)
+    net.load_state_dict(sd, strict=True)
+    net = net.cuda().train()
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(1, 1, 16, 16, 16, generator=g)
+    ref = oracle.unet3d_forward(sd, x, train=True)
+    eng = net.engine
+    ran_pair = []
+    inner = eng.forward_pair
+    eng.forward_pair = lambda *a, **k: (ran_pair.append(1), inner(*a, **k))[1]
+    _poison_allocator()
+    with torch.no_grad():
+        logits = net(x.cuda())
+    torch.cuda.synchronize()
+    return net, logits.cpu(), ref, bool(ran_pair)
+
+
+# The reference's UNet3D wires s_block2 / s_block1 so that level_channels = [l1, l2, 2 * l2] with bottleneck_channel = 4 * l2 are the
+# only widths whose forward exists, and the direct first-layer kernels take l1 / 2 = 8 * 2^j output channels.  Does the pair forward
+# cover a configuration?  [128, 128, 256]: 64-multiples other than the default -- yes; [32, 128, 256]: the 16-channel conv cannot be
+# padded to 64 channels inside its 32-channel pair buffer -- no; [32, 64, 128]: that, and the head kernel reads 64 channels -- no
+@pytest.mark.parametrize("levels,bott,pair", [([32, 128, 256], 512, False), ([128, 128, 256], 512, True), ([32, 64, 128], 256, False)])
+def test_unet3d_narrow_levels_default_mode_vs_oracle(levels, bott, pair):
+    """UNet3D(1, 2, level_channels=...) as built by default ("auto") against the fp32 oracle, whatever the allocator hands out
+    (every torch.empty of the forward finds NaN bit patterns): the pair forward where it has a layout (the default mode's
+    limits), the 16-bit engine elsewhere (the limits of test_unet3d_multi_channel_input_vs_oracle) -- never NaN logits, never an
+    argument error from a kernel.  A zero segment behind the valid lo channels (0 * NaN) cannot come out of segs3d any more
+    (tests/test_pair_reference_cpu.py); with the widths above it could not before either, so this test pins the fall-back and
+    the finiteness, not that fault."""
+    from semantic_segmentation_amd.unet3d import UNet3D
+    eng = UNet3D(1, 2, level_channels=levels, bottleneck_channel=bott).engine
+    assert eng.auto and eng.plan is not None
+    try:
+        eng._pair_layout(16)
+        covered = True
+    except NotImplementedError:
+        covered = False
+    assert covered == pair
+    net, logits, ref, ran_pair = _narrow_run(levels, bott, None, seed=41)
+    assert torch.isfinite(logits).all()
+    assert ran_pair == pair
+    d = (logits - ref).abs()
+    REPORT["narrow_%d_%d_%d" % tuple(levels)] = {"pair": ran_pair, "logit_max_abs": float(d.max()), "logit_mean_abs": float(d.mean())}
+    _dump()
+    if ran_pair:
+        assert float(d.max()) < LIMITS["default"]["max"] and float(d.mean()) < LIMITS["default"]["mean"], (float(d.max()), float(d.mean()))
+    else:
+        assert float(d.mean()) < 2e-3 and float(d.max()) < 2e-2, (float(d.mean()), float(d.max()))
+
+
 def test_unet3d_descent_direction():
     from semantic_segmentation_amd.unet3d import UNet3D
     sd = oracle.unet3d_state_dict(1, 2, seed=61)

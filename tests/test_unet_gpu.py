@@ -825,6 +825,23 @@ def test_pair_forward_segment_modes_run(mode):
     assert d.max() < 6.5e-3 and d.mean() < 9e-4
 
 
+def test_pair_forward_segment_modes_are_ordered():
+    """what separates the modes of test_pair_forward_segment_modes_run (all three pass its 6.5e-3): on the same input, the x_lo
+    segment on every stage brings the logits strictly closer to the oracle (mean |dlogit|) than none, and both correction
+    segments closer than either -- a correction segment that reads the wrong channels would not"""
+    from semantic_segmentation_amd.unet import unet_engine as ue
+    x, mask = oracle.synthetic_batch(2, 96, seed=21)
+    mean = {}
+    for mode in ("1", "x", "xw"):
+        net, sd = build_mode(2, 19, {s_: mode for s_ in ue.STAGES})
+        net.train()
+        ref = oracle.unet_forward(sd, x, True)
+        mean[mode] = float((net(x.cuda()).detach().cpu() - ref).abs().mean())
+    REPORT["segmode_order"] = mean
+    _dump()
+    assert mean["x"] < mean["1"] and mean["xw"] < mean["x"] and mean["xw"] < mean["1"], mean
+
+
 # ------------------------------------------------------------------------------------------------ RGB input, fused eval
 @pytest.mark.parametrize("precise", [None, False, True])
 def test_unet_rgb_input_vs_oracle(precise):
