@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GS_ABI_VERSION 50
+#define GS_ABI_VERSION 51
 
 enum GsDtype { GS_F16 = 0, GS_BF16 = 1 };
 enum GsStatus { GS_OK = 0, GS_EINVAL = -1, GS_ELAUNCH = -2, GS_EUNSUPPORTED = -3 };
@@ -563,8 +563,20 @@ int gs_bn_act_apply_split(const void* y_hi, const void* y_lo, const float* scale
 int gs_bn_act_apply_split_pool3d(const void* y_hi, const void* y_lo, const float* scale, const float* shift, int act, void* z_hi, void* z_lo,
                                  int z_pix_stride, int z_coff, void* zp_hi, void* zp_lo, int zp_pix_stride, int NB, int D, int H, int W, int C,
                                  int dtype, void* stream);
+/* OutConv (unet/unet_model.py:24, unet/unet_parts.py:74) on a dense pair: Cin == 64, Cout = 1..64 classes, fp32 NCHW logits.  1..4
+ * classes run the 8-lanes-per-pixel kernel; 5..64 classes one launch of a thread-per-pixel kernel with the weights in LDS. */
 int gs_head1x1_fwd_split(const void* x_hi, const void* x_lo, const float* w, const float* bias, float* y, int N, int H,
                          int W, int Cin, int Cout, int dtype, void* stream);
+/* The first conv of the pair forward for any input channel count: DoubleConv's Conv2d(n_channels, 64, 3, padding=1)
+ * (unet/unet_model.py:8-24, unet/unet_parts.py:16) with n_channels > 4, and the first Conv3d of UNet3D
+ * (GenSeg-3D/UNet3D/unet3d.py:89-126 with in_channels > 1) as a 2-D conv over in_channels * 3 depth-unfolded slices.
+ * x fp32 NCHW [N,Cin,H,W], w fp32 [Cout][Cin][3][3], both unrounded: fp32 products accumulated in fp32 on the fp32-input MFMA
+ * (csrc/stem_wide.hip).  y_hi / y_lo: dense [N,H,W,Cout] 16-bit pair, 16-byte aligned.  bn_partials: NULL, or
+ * [gs_conv_widecin_mtiles(N,H,W)][2][Cout] rows of sum(y), sum(y^2) for gs_bn_finalize.  No atomics: runs are bit-identical.
+ * Cin 1..64, Cout in {32, 64, 96, 128}; GS_EUNSUPPORTED (no error string, nothing launched) otherwise. */
+int gs_conv_widecin_mtiles(int N, int H, int W);
+int gs_conv_widecin_fwd_split(const float* x, const float* w, void* y_hi, void* y_lo, float* bn_partials, int N, int Cin, int H,
+                              int W, int Cout, int dtype, void* stream);
 /* Pair-forward forms of the "never stored" edge kernels (mixed mode; gs_stem_fwd_bn / gs_head1x1_bn_fwd of the default engine):
  * gs_head1x1_bn_fwd_split: OutConv on act(scale * (y_hi + y_lo) + shift) of the last stage's conv-output pair.
  * gs_stem_fwd_bn_pair: the one-channel stem conv + BatchNorm + activation in one pass -> z_hi / z_lo (pixel stride

@@ -614,6 +614,71 @@ __global__ __launch_bounds__(256) void head1x1_split_kernel(const HeadSArgs a) {
     }
 }
 
+// Wide head (5..64 classes, unet/unet_model.py:24 with n_classes > 4): ONE THREAD PER PIXEL joins the 64-channel pair in fp32 once
+// (BatchNorm + activation on the load path as above) and produces every class in one launch -- the head weights sit in LDS as
+// [ci][classes padded to 4] and are read at wave-uniform addresses, four classes at a time in registers.  Each class is the sum of
+// eight 8-term chains added as a tree, the order of head1x1_split_kernel.  Logit stores are coalesced along the pixel.
+template <int DT>
+__global__ __launch_bounds__(256) void head1x1_wide_split_kernel(const HeadSArgs a) {
+    __shared__ __attribute__((aligned(16))) float wl[64 * 64];
+    __shared__ float bl[64], scl[64], shl[64];
+    const int CP = (a.Cout + 3) & ~3;
+    for (int i = threadIdx.x; i < 64 * CP; i += 256) {
+        const int c = i % CP, ci = i / CP;
+        wl[i] = c < a.Cout ? a.w[c * 64 + ci] : 0.f;
+    }
+    if (threadIdx.x < 64) {
+        bl[threadIdx.x] = ((int)threadIdx.x < a.Cout && a.bias) ? a.bias[threadIdx.x] : 0.f;
+        scl[threadIdx.x] = a.scale ? a.scale[threadIdx.x] : 1.f;
+        shl[threadIdx.x] = a.scale ? a.shift[threadIdx.x] : 0.f;
+    }
+    __syncthreads();
+    const float slope = a.act == GS_ACT_RELU ? 0.f : (a.act == GS_ACT_LEAKY02 ? 0.2f : 1.f);
+    const int M = a.N * a.HW;
+    for (int m = blockIdx.x * 256 + threadIdx.x; m < M; m += gridDim.x * 256) {
+        float v[64];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float v8[8];
+            join8<DT>(*reinterpret_cast<const uint4*>(a.x_hi + (int64_t)m * 64 + j * 8),
+                      *reinterpret_cast<const uint4*>(a.x_lo + (int64_t)m * 64 + j * 8), v8);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                float t = v8[i];
+                if (a.scale) {
+                    t = t * scl[j * 8 + i] + shl[j * 8 + i];
+                    t = t > 0.f ? t : t * slope;
+                }
+                v[j * 8 + i] = t;
+            }
+        }
+        const int n = m / a.HW, hw = m - n * a.HW;
+        float* yp = a.y + (int64_t)n * a.Cout * a.HW + hw;
+        for (int c0 = 0; c0 < a.Cout; c0 += 4) {
+            float t[8][4];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) t[j][c] = 0.f;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const float4 w4 = *reinterpret_cast<const float4*>(wl + (j * 8 + i) * CP + c0);
+                    t[j][0] += v[j * 8 + i] * w4.x;
+                    t[j][1] += v[j * 8 + i] * w4.y;
+                    t[j][2] += v[j * 8 + i] * w4.z;
+                    t[j][3] += v[j * 8 + i] * w4.w;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c0 + c < a.Cout) {
+                    const float s = ((t[0][c] + t[1][c]) + (t[2][c] + t[3][c])) + ((t[4][c] + t[5][c]) + (t[6][c] + t[7][c]));
+                    yp[(int64_t)(c0 + c) * a.HW] = s + bl[c0 + c];
+                }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int gs_pack_weight_split(const float* w, void* pack, int Cout, int Cin, int taps, int transposed, int dtype,
@@ -844,7 +909,8 @@ extern "C" int gs_head1x1_fwd_split(const void* x_hi, const void* x_lo, const fl
 static int head1x1_split_impl(const void* x_hi, const void* x_lo, const float* scale, const float* shift, int act, const float* w,
                               const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int dtype, void* stream) {
     GS_CHECK_ARG(x_hi && x_lo && w && y && N > 0 && H > 0 && W > 0, "gs_head1x1_fwd_split: bad arguments");
-    GS_CHECK_ARG(Cin == 64 && Cout >= 1 && Cout <= 4, "gs_head1x1_fwd_split: Cin must be 64 and Cout 1..4");
+    GS_CHECK_ARG(Cin == 64 && Cout >= 1 && Cout <= 64, "gs_head1x1_fwd_split: Cin must be 64 and Cout 1..64");
+    GS_CHECK_ARG((((uintptr_t)x_hi | (uintptr_t)x_lo) & 15) == 0, "gs_head1x1_fwd_split: x_hi / x_lo must be 16-byte aligned");
     GS_CHECK_ARG((int64_t)N * H * W + 256 < 2147483647LL, "gs_head1x1_fwd_split: too many pixels");
     GS_CHECK_ARG(dtype == GS_F16 || dtype == GS_BF16, "gs_head1x1_fwd_split: bad dtype");
     HeadSArgs a{(const unsigned short*)x_hi, (const unsigned short*)x_lo, w, bias, y, N, H * W, Cout};
@@ -852,6 +918,15 @@ static int head1x1_split_impl(const void* x_hi, const void* x_lo, const float* s
     int64_t hb = cdiv64((int64_t)N * H * W, 32);
     if (hb > 8192) hb = 8192;
     hipStream_t s = (hipStream_t)stream;
+    if (Cout > 4) {                                        // every class in one launch; launches of 1..4 classes keep their kernel
+        GS_CHECK_ARG((int64_t)N * H * W + 8192 * 256 < 2147483647LL, "gs_head1x1_fwd_split: too many pixels");
+        int64_t wb = cdiv64((int64_t)N * H * W, 256);
+        if (wb > 8192) wb = 8192;
+        if (dtype == GS_F16) head1x1_wide_split_kernel<GS_F16><<<(int)wb, 256, 0, s>>>(a);
+        else head1x1_wide_split_kernel<GS_BF16><<<(int)wb, 256, 0, s>>>(a);
+        GS_CHECK_LAUNCH("gs_head1x1_fwd_split");
+        return GS_OK;
+    }
     if (dtype == GS_F16) head1x1_split_kernel<GS_F16><<<(int)hb, 256, 0, s>>>(a);
     else head1x1_split_kernel<GS_BF16><<<(int)hb, 256, 0, s>>>(a);
     GS_CHECK_LAUNCH("gs_head1x1_fwd_split");

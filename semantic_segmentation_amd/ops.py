@@ -1374,6 +1374,33 @@ def conv_smallcin_fwd_split(x, w, y_hi, y_lo, bn_partials, k, pad):
               dt_code(y_hi), _stream())
 
 
+def conv_widecin_mtiles(N, H, W) -> int:
+    """BatchNorm partial rows conv_widecin_fwd_split writes: one per 8 x 32 pixel patch."""
+    return _lib.load().gs_conv_widecin_mtiles(N, H, W)
+
+
+def conv_widecin_fwd_split(x, w, y_hi, y_lo, bn_partials=None):
+    """First 3x3 conv (pad 1) on an fp32 NCHW image of 1..64 channels with fp32 weights [Cout,Cin,3,3], Cout in {32, 64, 96, 128}
+    -> dense pair y_hi / y_lo [N,H,W,Cout]; bn_partials: None or conv_widecin_mtiles(N,H,W) * 2 * Cout floats."""
+    _dev(x)
+    _f32(x, "x"); _f32(w, "w")
+    N, Cin, H, W = x.shape
+    Cout = y_hi.shape[3]
+    if tuple(y_hi.shape) != (N, H, W, Cout) or y_lo.shape != y_hi.shape or not (y_hi.is_contiguous() and y_lo.is_contiguous()):
+        raise ValueError("conv_widecin_fwd_split: y_hi / y_lo must be dense [N,H,W,Cout]")
+    if tuple(w.shape) != (Cout, Cin, 3, 3) or not (x.is_contiguous() and w.is_contiguous()):
+        raise ValueError("conv_widecin_fwd_split: x dense [N,Cin,H,W], w dense [Cout,Cin,3,3]")
+    if bn_partials is not None:
+        _f32(bn_partials, "bn_partials")
+        if bn_partials.numel() < conv_widecin_mtiles(N, H, W) * 2 * Cout:
+            raise ValueError("conv_widecin_fwd_split: bn_partials needs conv_widecin_mtiles(N,H,W) * 2 * Cout floats")
+    rc = _lib.load().gs_conv_widecin_fwd_split(_p(x), _p(w), _p(y_hi), _p(y_lo), _p(bn_partials), N, Cin, H, W, Cout,
+                                               dt_code(y_hi), _stream())
+    if rc == _lib.GS_EUNSUPPORTED:
+        raise NotImplementedError(f"conv_widecin_fwd_split: Cin={Cin} (1..64) / Cout={Cout} (32, 64, 96, 128) not covered")
+    _lib.check(rc, "gs_conv_widecin_fwd_split")
+
+
 def bn_act_apply_split(y_hi, y_lo, scale, shift, act, z_hi, z_lo, z_stride, z_coff, zp_hi=None, zp_lo=None, zp_stride=0):
     """z pair = act(scale * (y_hi + y_lo) + shift); y_hi / y_lo dense [N,H,W,C]; optional 2x2 max-pooled pair."""
     N, H, W, C = y_hi.shape
@@ -1402,19 +1429,24 @@ def head1x1_bn_fwd_split(y_hi, y_lo, scale, shift, act, w, bias, logits):
     N, H, W, C = y_hi.shape
     ncls = logits.shape[1]
     if (C != 64 or y_lo.shape != y_hi.shape or tuple(logits.shape) != (N, ncls, H, W) or w.numel() != ncls * 64
+            or not 1 <= ncls <= 64 or (bias is not None and bias.numel() != ncls)
             or not (y_hi.is_contiguous() and y_lo.is_contiguous() and logits.is_contiguous())):
-        raise ValueError("head1x1_bn_fwd_split: y pair [N,H,W,64] dense, logits [N,ncls,H,W], w [ncls,64]")
+        raise ValueError("head1x1_bn_fwd_split: y pair [N,H,W,64] dense, logits [N,ncls,H,W] with 1..64 classes, w [ncls,64]")
     _lib.call("gs_head1x1_bn_fwd_split", _p(y_hi), _p(y_lo), _p(scale), _p(shift), act, _p(w), _p(bias), _p(logits), N, H, W, 64,
               ncls, dt_code(y_hi), _stream())
 
 
 def head1x1_fwd_split(x_hi, x_lo, w, bias, y):
-    """OutConv 1x1 on a dense pair [N,H,W,64] -> fp32 NCHW logits."""
+    """OutConv 1x1 on a dense pair [N,H,W,64] -> fp32 NCHW logits, 1..64 classes (more than four: one launch of the wide kernel)."""
     _dev(x_hi)
     _f32(w, "w"); _f32(bias, "bias"); _f32(y, "y")
     N, H, W, Cin = x_hi.shape
     if not (x_hi.is_contiguous() and x_lo.is_contiguous()) or x_lo.shape != x_hi.shape:
         raise ValueError("head1x1_fwd_split: x_hi / x_lo must be dense NHWC of one shape")
+    ncls = y.shape[1]
+    if (tuple(y.shape) != (N, ncls, H, W) or not 1 <= ncls <= 64 or w.numel() != ncls * Cin
+            or (bias is not None and bias.numel() != ncls)):
+        raise ValueError("head1x1_fwd_split: logits [N,ncls,H,W] with 1..64 classes, w [ncls,Cin], bias [ncls]")
     _lib.call("gs_head1x1_fwd_split", _p(x_hi), _p(x_lo), _p(w), _p(bias), _p(y), N, H, W, Cin, y.shape[1], dt_code(x_hi),
               _stream())
 

@@ -20,6 +20,7 @@ from __future__ import annotations
 import functools
 import math
 import os
+import warnings
 from typing import Callable, Dict, List, Optional
 
 import torch
@@ -103,6 +104,7 @@ def pack_reuse_allowed(need_grad: bool, trust_versions: bool = False) -> bool:
     return PACK_CACHE and (PACK_CACHE_TRAINING or trust_versions or not need_grad)
 
 
+STEM_WKEY = "inc.double_conv.0.weight"                      # the image-end conv: told apart by name, its Cin may be a multiple of 8
 STAGES = (["inc.0", "inc.3"] + [f"down{i}.{k}" for i in range(1, 5) for k in (0, 3)] +
           [s_ for j in range(1, 5) for s_ in (f"up{j}.up", f"up{j}.conv.0", f"up{j}.conv.3")])
 # MFMA segments of one stage of the pair forward: "1" = x_hi.w_hi, "x" = + x_lo.w_hi, "w" = + x_hi.w_lo, "xw" = all three
@@ -181,6 +183,7 @@ class UNetEngine:
         # "auto" (what UNet() builds): the mixed pair forward wherever it is implemented, the 16-bit engine elsewhere (an
         # explicit "mixed" / True raises there instead)
         self.auto = precise == "auto"
+        self._warned_fallback = False    # "auto" names its fallback to the 16-bit engine once per engine
         self.dynamic_loss_scale = os.environ.get("GSSEG_DYNAMIC_LOSS_SCALE", "0") == "1"
         self.tdt = _TORCH_DT[dtype]
         self._packs: Dict[str, tuple] = {}
@@ -251,7 +254,7 @@ class UNetEngine:
                     continue
                 cin, cout = w.shape[0], w.shape[1]
             else:
-                if tuple(w.shape[2:]) != (3, 3) or w.shape[1] % 8 != 0:      # the image-end layer is not packed
+                if tuple(w.shape[2:]) != (3, 3) or name == STEM_WKEY:         # the image-end layer is not packed (any channel count)
                     continue
                 cout, cin = w.shape[0], w.shape[1]
             key = _pack_key(w)
@@ -336,11 +339,23 @@ class UNetEngine:
         if H < 16 or W < 16:
             raise ValueError("input must be at least 16x16 (four 2x2 poolings)")
         if self.precise:
-            covered = net.n_channels <= 4 and net.n_classes <= 4 and ops.USE_HALO_CONV
-            if covered or not self.auto:
-                if net.n_channels > 4 or net.n_classes > 4:
-                    raise NotImplementedError("the pair forward supports n_channels / n_classes up to 4 (the direct end kernels)")
+            # what the pair forward does not cover: the end kernels stop at 64 image channels / classes (gs_conv_widecin_fwd_split,
+            # gs_head1x1_fwd_split); "auto" then runs the 16-bit engine, which takes any count, and says so once
+            why = None
+            if not ops.USE_HALO_CONV:
+                why = "GSSEG_CONV3X3 is not 'halo' (the pair forward needs the halo-reuse conv kernel)"
+            elif net.n_channels > 64 or net.n_classes > 64:
+                why = f"the pair forward's end kernels take up to 64 image channels and classes (got {net.n_channels}, {net.n_classes})"
+            if why is None:
                 return self.forward_precise(x, params, training, need_grad)
+            if not self.auto:
+                if ops.USE_HALO_CONV:
+                    raise NotImplementedError("UNet pair forward: " + why)
+                return self.forward_precise(x, params, training, need_grad)      # (raises: no halo-reuse conv kernel)
+            if not self._warned_fallback:
+                self._warned_fallback = True
+                warnings.warn(f"UNet(precise='auto'): {why} -- running the single 16-bit engine, whose logits are about 5e-3 from "
+                              "the fp32 reference instead of 1e-3", RuntimeWarning, stacklevel=2)
         dev, tdt = x.device, self.tdt
         x = x.contiguous().float()
         bufs = self.buffer_dict()
@@ -586,7 +601,7 @@ class UNetEngine:
             if w is None or w.dim() != 4:
                 continue
             cin, cout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
-            if cin % 8 != 0:                               # the image-end layer is not packed
+            if st == "inc.0":                              # the image-end layer is not packed (any channel count)
                 continue
             lo_len = None
             if not full:
@@ -628,7 +643,7 @@ class UNetEngine:
             prefix = blk if (blk == "inc" or blk.endswith(".conv")) else blk + ".maxpool_conv.1"
             wkey, bnkey = f"{prefix}.double_conv.{idx}.weight", f"{prefix}.double_conv.{int(idx) + 1}"
             w = params.get(wkey)
-            if w is None or w.dim() != 4 or w.shape[1] % 8 != 0:
+            if w is None or w.dim() != 4 or st == "inc.0":
                 continue                                   # (the image-end stem folds nothing: it is one pass already)
             rm, rv = bufs.get(bnkey + ".running_mean"), bufs.get(bnkey + ".running_var")
             if rm is None or rv is None:
@@ -710,7 +725,7 @@ class UNetEngine:
             if m_ == "q":
                 w_ = params.get(self._wkey_of(st_))
                 lv = lvl_of[st_.split(".")[0]]
-                ok = (not st_.endswith(".up") and w_ is not None and self.dtype == "f16"
+                ok = (not st_.endswith(".up") and st_ != "inc.0" and w_ is not None and self.dtype == "f16"
                       and ops.conv3x3_q8_ok(ws_[lv], w_.shape[1], w_.shape[0]))
                 if not ok:
                     eff[st_] = "xw"
@@ -766,10 +781,11 @@ class UNetEngine:
             batch_stats = training or rm is None
             rec = _ConvRec()
             rec.name, rec.wkey, rec.bnkey = f"{prefix}.{idx}", wkey, bnkey
-            rec.cin, rec.cout, rec.h, rec.w, rec.inp_is_image = cin, cout, h, w, image
+            wide_img = image and cin > 4                    # more than four image channels: the fp32 MFMA stem (csrc/stem_wide.hip)
+            rec.cin, rec.cout, rec.h, rec.w, rec.inp_is_image = cin, cout, h, w, image and not wide_img
             rec.inp, rec.train_stats, rec.geom, rec.z, rec.tap_sums = inp, batch_stats, None, None, None
             rec.inp_stride = None if image else 2 * cin
-            ntiles = ops.conv_smallcin_mtiles(N, h, w) if image else (
+            ntiles = ops.conv_widecin_mtiles(N, h, w) if wide_img else ops.conv_smallcin_mtiles(N, h, w) if image else (
                 ops.conv3x3_stat_rows(N, h, w, 2 * cin, cout, pair="q") if plan[short] == "q" else ops.conv3x3_stat_rows(N, h, w, cin, cout, pair=True))
             partials = empty(ops.bn_partials_numel(ntiles, cout), dtype=torch.float32) if batch_stats else None
             want_lo, zp_want_lo = int(want_lo), int(zp_want_lo)     # 0 none / 1 16-bit lo plane / 2 q plane (lo_fmt below)
@@ -806,7 +822,17 @@ class UNetEngine:
                                             N, h, w, cout)
                 return None
             y_hi, y_lo = empty(N, h, w, cout), empty(N, h, w, cout)
-            if image:
+            if wide_img:
+                # the conv-output pair and the statistics from the fp32 image and weights: no 16-bit image in the forward
+                ops.conv_widecin_fwd_split(inp, wparam.detach().contiguous(), y_hi, y_lo, partials)
+                if need_grad:
+                    # what the backward's wide image stage reads (as the 16-bit engine's forward builds it): the image as a 16-bit
+                    # NHWC tensor zero-padded to a multiple of 8 channels, the weight's data-gradient pack padded alike
+                    cpad = (cin + 7) // 8 * 8
+                    xin = (torch.zeros if cpad != cin else torch.empty)((N, h, w, cpad), dtype=tdt, device=dev)
+                    ops.nchw_to_nhwc(inp, xin, dst_stride=cpad)
+                    rec.inp, rec.cin, rec.wide = xin, cpad, cin
+            elif image:
                 ops.conv_smallcin_fwd_split(inp, wparam.detach().contiguous(), y_hi, y_lo, partials, 3, 1)
             elif plan[short] == "q":
                 qpack, wexp = self._seg_pack(wkey)
@@ -817,7 +843,10 @@ class UNetEngine:
                                  bn_partials=partials)
             coef = bn_coef(bnkey, partials, ntiles, cout, N * h * w, batch_stats)
             rec.y, rec.coef = y_hi, coef
-            rec.wd = None if image else (self._packed(wkey, wparam, False, True, need_fwd=False)[1] if need_grad else None)
+            if wide_img:
+                rec.wd = self._packed_padded(wkey, wparam, rec.cin, True)[1] if need_grad else None
+            else:
+                rec.wd = None if image else (self._packed(wkey, wparam, False, True, need_fwd=False)[1] if need_grad else None)
             if need_grad:
                 recs.append(rec)
             if to_head:

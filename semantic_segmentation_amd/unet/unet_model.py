@@ -37,7 +37,8 @@ class UNet(nn.Module):
         # north star asks for logits within 1e-3 of it, so the DEFAULT is the mode that meets that bound:
         #   precise=None / "auto" (GSSEG_PRECISE unset or "auto"): the "mixed" pair forward -- every tensor a hi/lo pair of 16-bit
         #       values, correction MFMA segments on the stages that make the 16-bit error (unet_engine.MIXED_XW): max |dlogit| < 1e-3.
-        #       Configurations the pair forward does not cover (more than 4 input channels / classes) run the 16-bit engine.
+        #       It covers up to 64 image channels and 64 classes; beyond that, or without the halo-reuse conv kernel
+        #       (GSSEG_CONV3X3 != halo), it runs the 16-bit engine, with one RuntimeWarning per object.
         #   precise="mixed" (GSSEG_PRECISE=mixed): the same, but unsupported configurations raise instead of falling back.
         #   precise=True (GSSEG_PRECISE=1): three MFMA segments everywhere, logits ~1e-5 from fp32 at ~3x the forward MFMA work.
         #   precise=False (GSSEG_PRECISE=0): the FAST mode -- single 16-bit storage, logits within ~4e-3, loss / Dice within 1e-5.

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import math
 import os
+import warnings
 from typing import Dict, List
 
 import torch
@@ -128,6 +129,7 @@ class UNet3DEngine:
         # to the 16-bit engine for configurations the pair forward does not cover.
         self.plan = resolve_plan3d(precise, dtype)
         self.auto = precise == "auto"
+        self._warned_fallback = False    # "auto" names its fallback to the 16-bit engine once per engine
         # data-parallel hooks (parallel.GradReducer.attach): gradients announced as they become final, the compute stream
         # waits for the collectives at the end of backward, autograd receives the reduced gradients
         self.grad_ready_hook = None
@@ -146,13 +148,20 @@ class UNet3DEngine:
             raise ValueError("volume dims must be multiples of 8 (three 2x2x2 poolings, no padding in the reference)")
         if self.plan is not None:
             if self.auto:
-                try:
-                    self._pair_layout(W0)
-                    covered = net.in_channels == 1 and net.num_classes <= 4 and ops.USE_HALO_CONV
-                except NotImplementedError:
-                    covered = False
-                if covered:
+                why = None
+                if not ops.USE_HALO_CONV:
+                    why = "GSSEG_CONV3X3 is not 'halo' (the pair forward needs the halo-reuse conv kernels)"
+                else:
+                    try:
+                        self._pair_layout(W0)
+                    except NotImplementedError as e:
+                        why = str(e)
+                if why is None:
                     return self.forward_pair(x, training, need_grad)
+                if not self._warned_fallback:
+                    self._warned_fallback = True
+                    warnings.warn(f"UNet3D(precise='auto'): {why} -- running the single 16-bit engine, whose logits are 2.4e-3 to "
+                                  "2.9e-3 from the fp32 reference instead of 1e-3", RuntimeWarning, stacklevel=2)
             else:
                 return self.forward_pair(x, training, need_grad)
         dev = x.device
@@ -337,8 +346,11 @@ class UNet3DEngine:
                 return ("q", 2 * cin, 2 * cin) if plan[name] == "q" else segs3d(plan[name], cin, **kw)
             if k != "a_block1":
                 lay[k + ".conv1"] = seg_or_q(k + ".conv1", blk.conv1.in_channels)
-            elif net.in_channels != 1:
-                raise NotImplementedError("pair forward: one input channel (the direct first-layer kernel)")
+            elif net.in_channels != 1 and not (net.in_channels * 3 <= 64 and blk.conv1.out_channels % 32 == 0
+                                               and 32 <= blk.conv1.out_channels <= 128):
+                # (in_channels == 1: gs_conv_smallcin_fwd_split on the three depth slices; more: gs_conv_widecin_fwd_split on 3 * C)
+                raise NotImplementedError("pair forward: the multi-channel first conv needs in_channels <= 21 and a first width "
+                                          f"of 32, 64, 96 or 128 (got {net.in_channels} -> {blk.conv1.out_channels})")
             lay[k + ".conv2"] = seg_or_q(k + ".conv2", blk.conv2.in_channels)
         for k, sb, ab in (("s_block3", net.s_block3, net.a_block3), ("s_block2", net.s_block2, net.a_block2),
                           ("s_block1", net.s_block1, net.a_block1)):
@@ -348,6 +360,8 @@ class UNet3DEngine:
                 segs3d(plan[k + ".conv2"], sb.conv2.in_channels)
         if net.s_block1.conv2.out_channels != 64:
             raise NotImplementedError("pair forward: the pointwise head kernel reads 64 channels")
+        if net.num_classes > 4:
+            raise NotImplementedError("pair forward: num_classes above 4 is not supported by the head's backward kernel")
         cache[W0] = (lay, plan)
         return cache[W0]
 
@@ -433,7 +447,26 @@ class UNet3DEngine:
             st.inp, st.in_stride, st.in_coff, st.wide, st.geom, st.x3 = inp, in_stride, 0, 0, None, None
             y_hi, y_lo = empty(NB * D, H, W, cout), empty(NB * D, H, W, cout)
             batch = training or bn.running_mean is None
-            if first:
+            if first and cin > 1:
+                # a multi-channel volume (unet3d.py:103-106): the depth-unfolded view per channel, X3[nb*D + d][c*3 + kd] =
+                # x[nb][c][d + kd - 1] (zero outside), through the fp32 MFMA stem with the weight viewed as [cout, C*3, 3, 3]
+                xp = F.pad(inp, (0, 0, 0, 0, 1, 1))
+                x3 = xp.unfold(2, 3, 1).permute(0, 2, 1, 5, 3, 4).reshape(NB * D, cin * 3, H, W).contiguous()
+                nt = ops.conv_widecin_mtiles(NB * D, H, W)
+                part = empty(ops.bn_partials_numel(nt, cout), dtype=torch.float32) if batch else None
+                ops.conv_widecin_fwd_split(x3, conv.weight.detach().reshape(cout, cin * 3, 3, 3).contiguous(), y_hi, y_lo, part)
+                st.wd, st.halo = None, False
+                if need_grad:
+                    # what the backward's wide first stage reads (as the 16-bit engine's forward builds it): the volume as a
+                    # 16-bit NDHWC tensor zero-padded to a multiple of 8 channels
+                    cpad = (cin + 7) // 8 * 8
+                    xin = (torch.zeros if cpad != cin else torch.empty)((NB * D, H, W, cpad), dtype=tdt, device=dev)
+                    ops.nchw_to_nhwc(inp.permute(0, 2, 1, 3, 4).reshape(NB * D, cin, H, W).contiguous(), xin, dst_stride=cpad)
+                    st.inp, st.in_stride, st.cin, st.wide, st.first = xin, cpad, cpad, cin, False
+                    st.halo = ops.conv3d3_eligible(cpad, cout)
+                    if not st.halo:
+                        st.geom = geom_conv3d(NB, D, H, W, cpad, cout, in_stride=cpad, in_coff=0)
+            elif first:
                 xp = F.pad(inp[:, 0], (0, 0, 0, 0, 1, 1))
                 x3 = xp.unfold(1, 3, 1).permute(0, 1, 4, 2, 3).reshape(NB * D, 3, H, W).contiguous()
                 st.x3 = x3
@@ -479,7 +512,7 @@ class UNet3DEngine:
 
         # ---- analysis path ----
         enc = []
-        inp, in_stride, cin = x, None, 1
+        inp, in_stride, cin = x, None, net.in_channels
         for k, blk in enumerate(a_blocks, 1):
             D, H, W = dims[k - 1]
             cmid, cout = blk.conv1.out_channels, blk.conv2.out_channels
