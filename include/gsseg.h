@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GS_ABI_VERSION 51
+#define GS_ABI_VERSION 52
 
 enum GsDtype { GS_F16 = 0, GS_BF16 = 1 };
 enum GsStatus { GS_OK = 0, GS_EINVAL = -1, GS_ELAUNCH = -2, GS_EUNSUPPORTED = -3 };
@@ -452,7 +452,8 @@ int gs_seg_loss_bwd(const float* logits, const uint8_t* mask, const float* out, 
  * out[1 + b] = dice_b.  ws: gs_dice_batched_ws_floats(B) floats.
  * gs_eval_dice fuses the prediction of unet/evaluate.py:31,38-41 in front of it: sigmoid(logit) > 0.5 (C == 1) or the
  * arg-max class (first maximum), one item per (sample, foreground class); logits fp32 NCHW, mask uint8 [N][HW];
- * ws for B = N * max(1, C - 1) items, out[1 + N*max(1,C-1)]. */
+ * ws for B = N * max(1, C - 1) items, out[1 + N*max(1,C-1)].  C = 1..64 (unet/evaluate.py:34-40 takes any class count): up to
+ * four classes count in registers, 5..64 in an LDS histogram per block (integer counts, exact; HW < 2^28 there). */
 int64_t gs_dice_batched_ws_floats(int B);
 int gs_dice_coeff_batched(const float* p, const float* t, int B, int64_t n_per, float* ws, float* out, void* stream);
 int gs_eval_dice(const float* logits, const uint8_t* mask, int N, int C, int64_t HW, float* ws, float* out, void* stream);
@@ -567,6 +568,23 @@ int gs_bn_act_apply_split_pool3d(const void* y_hi, const void* y_lo, const float
  * classes run the 8-lanes-per-pixel kernel; 5..64 classes one launch of a thread-per-pixel kernel with the weights in LDS. */
 int gs_head1x1_fwd_split(const void* x_hi, const void* x_lo, const float* w, const float* bias, float* y, int N, int H,
                          int W, int Cin, int Cout, int dtype, void* stream);
+/* The wide pointwise head behind that forward: OutConv (unet/unet_parts.py:71-77) and the conv3 head of UNet3D
+ * (GenSeg-3D/UNet3D/unet3d.py:89-126, Conv3d(64, num_classes, 1) on [NB*D, H, W] slices) with 1..64 classes, Cin == 64.
+ * gs_head1x1_wide_fwd: the forward from ONE dense 16-bit plane x [N,H,W,64] (the 16-bit engines): the thread-per-pixel kernel of
+ *   gs_head1x1_fwd_split without its lo plane, the same class-sum order, one launch.  w fp32 [ncls][64], bias fp32 [ncls] or NULL,
+ *   y fp32 NCHW [N,ncls,H,W].
+ * gs_head1x1_wide_bwd: dl fp32 NCHW [N,ncls,H,W] (as the loss backward writes it, already times the loss scale; never rounded to
+ *   16 bits) -> dz[m][ci] = sum_c dl[m][c] * w[c][ci], dense NHWC dtype [N,H,W,64], the class sum in fp32 rounded once (one launch),
+ *   and dw[c][ci] += gscale * sum_m dl[m][c] * z[m][ci], db[c] += gscale * sum_m dl[m][c] (fp32, ACCUMULATE as
+ *   gs_conv_smallcout_bwd does; z = the stored 16-bit input of the head, the hi plane in the pair engines): per-block slabs in ws
+ *   (gs_head1x1_wide_bwd_ws_floats(N,H,W,ncls) floats) summed in a fixed order -- no atomics, runs are bit-identical.
+ *   dz may be NULL (z-gradient not wanted); dw and db may be NULL together (then z and ws are not read).
+ * x / z / dz / ws 16-byte aligned, N*H*W + 2^21 < 2^31, 1 <= ncls <= 64, dtype f16 / bf16: GS_EINVAL before any launch otherwise. */
+int64_t gs_head1x1_wide_bwd_ws_floats(int N, int H, int W, int ncls);
+int gs_head1x1_wide_bwd(const void* z, const float* w, const float* dl, void* dz, float* dw, float* db, float* ws, int N, int H,
+                        int W, int ncls, float gscale, int dtype, void* stream);
+int gs_head1x1_wide_fwd(const void* x, const float* w, const float* bias, float* y, int N, int H, int W, int ncls, int dtype,
+                        void* stream);
 /* The first conv of the pair forward for any input channel count: DoubleConv's Conv2d(n_channels, 64, 3, padding=1)
  * (unet/unet_model.py:8-24, unet/unet_parts.py:16) with n_channels > 4, and the first Conv3d of UNet3D
  * (GenSeg-3D/UNet3D/unet3d.py:89-126 with in_channels > 1) as a 2-D conv over in_channels * 3 depth-unfolded slices.

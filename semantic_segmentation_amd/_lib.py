@@ -18,7 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 GS_F16, GS_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LEAKY02, ACT_TANH = 0, 1, 2, 3
 GS_MAX_TAPS = 64
-ABI_VERSION = 51
+ABI_VERSION = 52
 
 
 class GsConvGeom(ctypes.Structure):
@@ -181,6 +181,9 @@ PROTOTYPES = {
     "gs_conv_widecin_mtiles": (c_int, [c_int, c_int, c_int]),
     "gs_conv_widecin_fwd_split": (c_int, [_F, _F, _P, _P, _F] + [c_int] * 6 + [c_void_p]),
     "gs_head1x1_fwd_split": (c_int, [_P, _P, _F, _F, _F] + [c_int] * 6 + [c_void_p]),
+    "gs_head1x1_wide_bwd_ws_floats": (c_int64, [c_int] * 4),
+    "gs_head1x1_wide_bwd": (c_int, [_P, _F, _F, _P, _F, _F, _F] + [c_int] * 4 + [c_float, c_int, c_void_p]),
+    "gs_head1x1_wide_fwd": (c_int, [_P, _F, _F, _F] + [c_int] * 5 + [c_void_p]),
     "gs_head1x1_bn_fwd_split": (c_int, [_P, _P, _F, _F, c_int, _F, _F, _F] + [c_int] * 6 + [c_void_p]),
     "gs_stem_fwd_bn_pair": (c_int, [_F, _F, _F, _F, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "gs_stem_bwd_onepass_strided": (c_int, [_F, _P, c_int, _P, c_int, c_int, c_int, _F, _F, c_int, c_int, c_int, c_int, c_void_p]),

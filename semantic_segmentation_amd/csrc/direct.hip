@@ -1299,6 +1299,164 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
     }
 }
 
+// ---- wide pointwise head, Cin == 64, 1..64 classes (unet_parts.py:71-77 with n_classes > 4; the conv3 head of
+// GenSeg-3D/UNet3D/unet3d.py): the backward of head1x1_wide_split_kernel (precise.hip), one launch per gradient for every
+// class count.  dl is the fp32 NCHW logit gradient as the loss backward writes it and is never rounded to 16 bits.
+struct HWArgs {
+    const unsigned short* z; const float* w; const float* dl; unsigned short* dz; float* slab; float* bslab;
+    int N, HW, Cout, pix_per_block;
+};
+
+// data gradient dz[m][ci] = sum_c dl[n][c][hw] * w[c][ci]: a thread holds the 64 sums of a pixel in fp32 registers (one fmaf
+// chain over the classes in ascending order, rounded once at the store), the weights sit in LDS as [class][64] and are read at
+// wave-uniform addresses, the dl loads are coalesced along the pixel (four classes in flight), stores are 8 x 16 bytes.
+// PX pixels per thread, 256 apart, share every weight read: at 64 classes the LDS reads of one pixel per thread take as long
+// as its FMAs on all four SIMDs together (batch 8, 256^2, 9 / 64 classes: one pixel 38 / 101 us, two pixels 34 / 84 us).
+constexpr int HW_DGRAD_PX = 2;
+template <int DT, int PX>
+__global__ __launch_bounds__(256) void head1x1_wide_dgrad_kernel(const HWArgs a) {
+    __shared__ __attribute__((aligned(16))) float wl[64 * 64];
+    const int CP = (a.Cout + 3) & ~3;
+    for (int i = threadIdx.x; i < CP * 64; i += 256) wl[i] = i < a.Cout * 64 ? a.w[i] : 0.f;
+    __syncthreads();
+    const int M = a.N * a.HW;                                // host guarantees M + grid * 256 * PX < 2^31
+    for (int mb = blockIdx.x * (256 * PX) + threadIdx.x; mb < M; mb += gridDim.x * (256 * PX)) {
+        const float* gp[PX];
+        float acc[PX][64];
+#pragma unroll
+        for (int u = 0; u < PX; ++u) {
+            const int m = mb + u * 256 < M ? mb + u * 256 : mb;             // past the end: pixel mb again, not stored
+            const int n = m / a.HW, hw = m - n * a.HW;
+            gp[u] = a.dl + (int64_t)n * a.Cout * a.HW + hw;
+#pragma unroll
+            for (int i = 0; i < 64; ++i) acc[u][i] = 0.f;
+        }
+        for (int c0 = 0; c0 < CP; c0 += 4) {
+            float g[PX][4];
+#pragma unroll
+            for (int u = 0; u < PX; ++u)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) g[u][k] = c0 + k < a.Cout ? gp[u][(int64_t)(c0 + k) * a.HW] : 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+#pragma unroll
+                for (int i = 0; i < 64; i += 4) {
+                    const float4 w4 = *reinterpret_cast<const float4*>(wl + (c0 + k) * 64 + i);
+#pragma unroll
+                    for (int u = 0; u < PX; ++u) {
+                        acc[u][i] = fmaf(g[u][k], w4.x, acc[u][i]);
+                        acc[u][i + 1] = fmaf(g[u][k], w4.y, acc[u][i + 1]);
+                        acc[u][i + 2] = fmaf(g[u][k], w4.z, acc[u][i + 2]);
+                        acc[u][i + 3] = fmaf(g[u][k], w4.w, acc[u][i + 3]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PX; ++u) {
+            const int m = mb + u * 256;
+            if (m >= M) continue;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                float o[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) o[i] = acc[u][j * 8 + i];
+                *reinterpret_cast<uint4*>(a.dz + (int64_t)m * 64 + j * 8) = pack8<DT>(o);
+            }
+        }
+    }
+}
+
+// weight + bias gradient dw[c][ci] = sum_m dl[m][c] * z[m][ci], db[c] = sum_m dl[m][c]: a block walks its pixels in stages of 64.
+// A stage puts z (unpacked to fp32, [pixel][64]) and dl ([class group of 4][pixel][4], zero past the block's last pixel) in LDS;
+// a thread owns a 4-class x 4-channel tile of dw (16 fp32 sums).  With G = ceil(Cout / 4) class groups 16 * G threads cover dw
+// once, so floor(16 / G) pixel lanes each take every floor(16 / G)-th pixel of a stage; the lanes are added in lane order at
+// the end.  Every sum has a fixed order: per-block slabs [Cout * 64] + bias partials [64], then slab_reduce_kernel.  No atomics.
+constexpr int HW_STAGE = 64;
+
+template <int DT>
+__global__ __launch_bounds__(256) void head1x1_wide_wgrad_kernel(const HWArgs a) {
+    __shared__ __attribute__((aligned(16))) float zt[HW_STAGE * 64];         // reused for the lane reduction: 256 threads x 16 sums
+    __shared__ __attribute__((aligned(16))) float dt[16 * HW_STAGE * 4];
+    __shared__ float bt[256 * 4];
+    const int G = (a.Cout + 3) >> 2, PL = 16 / G;
+    const int tci = threadIdx.x & 15, r = threadIdx.x >> 4;
+    const int cg = r % G, pl = r / G;                        // pl >= PL: the thread stages only
+    const int M = a.N * a.HW;
+    const int m0 = blockIdx.x * a.pix_per_block;
+    const int m1 = m0 + a.pix_per_block < M ? m0 + a.pix_per_block : M;
+    float acc[4][4], sb[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[c][i] = 0.f;
+    for (int ms = m0; ms < m1; ms += HW_STAGE) {
+        __syncthreads();
+        for (int q = threadIdx.x; q < HW_STAGE * 8; q += 256) {              // z: 16-byte chunks, consecutive lanes consecutive bytes
+            const int p = q >> 3, j = q & 7;
+            float v[8];
+            if (ms + p < m1) {
+                unpack8<DT>(*reinterpret_cast<const uint4*>(a.z + (int64_t)(ms + p) * 64 + j * 8), v);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = 0.f;
+            }
+            *reinterpret_cast<float4*>(zt + p * 64 + j * 8) = make_float4(v[0], v[1], v[2], v[3]);
+            *reinterpret_cast<float4*>(zt + p * 64 + j * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
+        }
+        for (int q = threadIdx.x; q < G * HW_STAGE; q += 256) {              // dl: four classes of one pixel, coalesced along the pixel
+            const int p = q % HW_STAGE, g = q / HW_STAGE;
+            float d[4] = {0.f, 0.f, 0.f, 0.f};
+            const int m = ms + p;
+            if (m < m1) {
+                const int n = m / a.HW, hw = m - n * a.HW;
+                const float* gp = a.dl + (int64_t)n * a.Cout * a.HW + hw;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (g * 4 + k < a.Cout) d[k] = gp[(int64_t)(g * 4 + k) * a.HW];
+            }
+            *reinterpret_cast<float4*>(dt + (g * HW_STAGE + p) * 4) = make_float4(d[0], d[1], d[2], d[3]);
+        }
+        __syncthreads();
+        if (pl < PL) {
+            for (int p = pl; p < HW_STAGE; p += PL) {
+                const float4 d4 = *reinterpret_cast<const float4*>(dt + (cg * HW_STAGE + p) * 4);
+                const float4 z4 = *reinterpret_cast<const float4*>(zt + p * 64 + tci * 4);
+                const float d[4] = {d4.x, d4.y, d4.z, d4.w}, zv[4] = {z4.x, z4.y, z4.z, z4.w};
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    sb[c] += d[c];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) acc[c][i] = fmaf(d[c], zv[i], acc[c][i]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        *reinterpret_cast<float4*>(zt + threadIdx.x * 16 + c * 4) = make_float4(acc[c][0], acc[c][1], acc[c][2], acc[c][3]);
+        bt[threadIdx.x * 4 + c] = sb[c];
+    }
+    __syncthreads();
+    if (pl == 0) {                                           // thread (cg, tci) adds the pixel lanes in order
+        float* slab = a.slab + (int64_t)blockIdx.x * a.Cout * 64;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (cg * 4 + c >= a.Cout) continue;
+            float s[4] = {0.f, 0.f, 0.f, 0.f}, b = 0.f;
+            for (int l = 0; l < PL; ++l) {
+                const int t = ((l * G + cg) << 4) + tci;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) s[i] += zt[t * 16 + c * 4 + i];
+                b += bt[t * 4 + c];
+            }
+            *reinterpret_cast<float4*>(slab + (cg * 4 + c) * 64 + tci * 4) = make_float4(s[0], s[1], s[2], s[3]);
+            if (tci == 0 && a.bslab) a.bslab[(int64_t)blockIdx.x * 64 + cg * 4 + c] = b;
+        }
+    }
+}
+
 }  // namespace
 
 // pixels per block of the two slab-writing weight-gradient kernels (stem and head): many blocks, each writes its partial
@@ -1680,4 +1838,54 @@ extern "C" int gs_head1x1_bn_wgrad(const void* y_conv, const float* bn_scale, co
     GS_CHECK_ARG(act == GS_ACT_NONE || act == GS_ACT_RELU || act == GS_ACT_LEAKY02, "gs_head1x1_bn_wgrad: activation %d not supported", act);
     return smallcout_bwd_impl(y_conv, w, dl, nullptr, dw, db, ws, N, H, W, 64, Cout, H, W, 1, 1, 0, gscale, dtype, stream,
                               bn_scale, bn_shift, head_bn_slope(act));
+}
+
+// ---- wide pointwise head backward (1..64 classes, Cin == 64): one data-gradient launch, one weight-gradient launch + the
+// ordered slab reductions.  1024 blocks (four per CU) of whole 64-pixel stages: at batch 8, 256^2 and 64 classes the slabs are
+// 17 MB against the 201 MB the kernel reads.  (measured there at 9 / 64 classes: 54 / 140 us with 512 blocks, 47 / 116 us with
+// 1024, 61 / 125 us with 2048, 83 / 232 us with 256.)
+static int64_t head_wide_ppb(int64_t M) {
+    int64_t ppb = cdiv64(M, 1024);
+    if (ppb < HW_STAGE) ppb = HW_STAGE;
+    return cdiv64(ppb, HW_STAGE) * HW_STAGE;
+}
+
+extern "C" int64_t gs_head1x1_wide_bwd_ws_floats(int N, int H, int W, int ncls) {
+    if (N <= 0 || H <= 0 || W <= 0 || ncls < 1 || ncls > 64) return 0;
+    const int64_t M = (int64_t)N * H * W;
+    return cdiv64(M, head_wide_ppb(M)) * ((int64_t)ncls * 64 + 64);
+}
+
+extern "C" int gs_head1x1_wide_bwd(const void* z, const float* w, const float* dl, void* dz, float* dw, float* db, float* ws,
+                                   int N, int H, int W, int ncls, float gscale, int dtype, void* stream) {
+    GS_CHECK_ARG(N > 0 && H > 0 && W > 0, "gs_head1x1_wide_bwd: bad dims");
+    GS_CHECK_ARG(ncls >= 1 && ncls <= 64, "gs_head1x1_wide_bwd: ncls=%d must be 1..64", ncls);
+    GS_CHECK_ARG(dtype == GS_F16 || dtype == GS_BF16, "gs_head1x1_wide_bwd: bad dtype");
+    GS_CHECK_ARG(w && dl && (dz || dw), "gs_head1x1_wide_bwd: null pointer");
+    GS_CHECK_ARG(dw || !db, "gs_head1x1_wide_bwd: db comes with dw");
+    GS_CHECK_ARG(!dw || (z && ws), "gs_head1x1_wide_bwd: dw needs z and a workspace");
+    GS_CHECK_ARG((((uintptr_t)z | (uintptr_t)dz | (uintptr_t)ws) & 15) == 0, "gs_head1x1_wide_bwd: z / dz / ws must be 16-byte aligned");
+    const int64_t M = (int64_t)N * H * W;
+    GS_CHECK_ARG(M + 8192 * 512 < 2147483647LL, "gs_head1x1_wide_bwd: too many pixels");
+    HWArgs a{(const unsigned short*)z, w, dl, (unsigned short*)dz, nullptr, nullptr, N, H * W, ncls, 0};
+    hipStream_t s = (hipStream_t)stream;
+    if (dz) {
+        int64_t nb = cdiv64(M, 256 * HW_DGRAD_PX);
+        if (nb > 8192) nb = 8192;
+        if (dtype == GS_F16) head1x1_wide_dgrad_kernel<GS_F16, HW_DGRAD_PX><<<(int)nb, 256, 0, s>>>(a);
+        else head1x1_wide_dgrad_kernel<GS_BF16, HW_DGRAD_PX><<<(int)nb, 256, 0, s>>>(a);
+    }
+    if (dw) {
+        const int64_t ppb = head_wide_ppb(M);
+        const int nb = (int)cdiv64(M, ppb), n = ncls * 64;
+        a.pix_per_block = (int)ppb;
+        a.slab = ws;                                 // partial slabs [nb][ncls * 64], then bias partials [nb][64]
+        a.bslab = db ? ws + (int64_t)nb * n : nullptr;
+        if (dtype == GS_F16) head1x1_wide_wgrad_kernel<GS_F16><<<nb, 256, 0, s>>>(a);
+        else head1x1_wide_wgrad_kernel<GS_BF16><<<nb, 256, 0, s>>>(a);
+        slab_reduce_kernel<<<cdiv(n, 32), 256, 0, s>>>(ws, nb, n, n, gscale, dw);
+        if (db) slab_reduce_kernel<<<cdiv(ncls, 32), 256, 0, s>>>(ws + (int64_t)nb * n, nb, 64, ncls, gscale, db);
+    }
+    GS_CHECK_LAUNCH("gs_head1x1_wide_bwd");
+    return GS_OK;
 }

@@ -318,6 +318,38 @@ __global__ __launch_bounds__(256) void eval_dice_kernel(const float* __restrict_
     }
 }
 
+// the same contract for 5..64 classes (K = C - 1 <= 63 items per sample): a block counts into an LDS histogram [K][inter, pred, true]
+// with integer LDS atomics (exact, order-free) and writes it out once, in index order, as fp32 counts (< 2^24 per block: the host
+// checks) in the workspace layout of eval_dice_kernel.  The logit loads are coalesced along the pixel.
+__global__ __launch_bounds__(256) void eval_dice_wide_kernel(const float* __restrict__ x, const uint8_t* __restrict__ m, int C,
+                                                             int64_t HW, float* __restrict__ ws) {
+    __shared__ unsigned int cnt[63 * 3];
+    const int K = C - 1;
+    for (int i = threadIdx.x; i < 3 * K; i += 256) cnt[i] = 0u;
+    __syncthreads();
+    const float* xp = x + (int64_t)blockIdx.y * C * HW;
+    const uint8_t* mp = m + (int64_t)blockIdx.y * HW;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < HW; i += (int64_t)gridDim.x * 256) {
+        const int t = mp[i];
+        float best = xp[i];
+        int pred = 0;
+        for (int c = 1; c < C; ++c) {
+            const float v = xp[(int64_t)c * HW + i];
+            if (v > best) { best = v; pred = c; }
+        }
+        if (pred > 0) {
+            atomicAdd(&cnt[(pred - 1) * 3 + 1], 1u);
+            if (pred == t) atomicAdd(&cnt[(pred - 1) * 3], 1u);
+        }
+        if (t > 0 && t < C) atomicAdd(&cnt[(t - 1) * 3 + 2], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 3 * K; i += 256) {
+        const int k = i / 3, q = i - 3 * k;
+        ws[(((int64_t)blockIdx.y * K + k) * DB_BLOCKS + blockIdx.x) * 3 + q] = (float)cnt[i];
+    }
+}
+
 // out[0] = mean of the B coefficients, out[1 + b] = dice_b
 // metric 0: Dice (dice_score.py:12-16); 1: Jaccard index with smooth = 1 (train_end2end_isic.py:40-53)
 __global__ __launch_bounds__(256) void dice_batched_finalize_kernel(const float* __restrict__ ws, int B, int nblk,
@@ -469,11 +501,16 @@ extern "C" int gs_dice_coeff_batched(const float* p, const float* t, int B, int6
 
 static int eval_metric(const float* logits, const uint8_t* mask, int N, int C, int64_t HW, int metric, float* ws, float* out,
                        void* stream, const char* who) {
-    GS_CHECK_ARG(logits && mask && ws && out && N > 0 && N <= 65535 && C >= 1 && C <= 4 && HW > 0, "%s: bad arguments (C <= 4)", who);
+    GS_CHECK_ARG(logits && mask && ws && out && N > 0 && N <= 65535 && C >= 1 && C <= (metric == 0 ? 64 : 4) && HW > 0,
+                 "%s: bad arguments (C <= %d)", who, metric == 0 ? 64 : 4);
     hipStream_t s = (hipStream_t)stream;
     const int K = C == 1 ? 1 : C - 1;
     const int nb = dice_batched_blocks(HW);
-    eval_dice_kernel<<<dim3(nb, N), 256, 0, s>>>(logits, mask, C, HW, ws);
+    if (C > 4) {                                   // 5..64 classes: the LDS-histogram kernel; 1..4 classes keep theirs
+        GS_CHECK_ARG(cdiv64(HW, nb) + 256 < (1 << 24), "%s: too many pixels per sample for exact fp32 block counts", who);
+        eval_dice_wide_kernel<<<dim3(nb, N), 256, 0, s>>>(logits, mask, C, HW, ws);
+    } else
+        eval_dice_kernel<<<dim3(nb, N), 256, 0, s>>>(logits, mask, C, HW, ws);
     dice_batched_finalize_kernel<<<1, 256, 0, s>>>(ws, N * K, nb, out, metric);
     GS_CHECK_LAUNCH(who);
     return GS_OK;

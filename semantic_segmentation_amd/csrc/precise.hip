@@ -618,7 +618,8 @@ __global__ __launch_bounds__(256) void head1x1_split_kernel(const HeadSArgs a) {
 // (BatchNorm + activation on the load path as above) and produces every class in one launch -- the head weights sit in LDS as
 // [ci][classes padded to 4] and are read at wave-uniform addresses, four classes at a time in registers.  Each class is the sum of
 // eight 8-term chains added as a tree, the order of head1x1_split_kernel.  Logit stores are coalesced along the pixel.
-template <int DT>
+// LO = false: the input is a single 16-bit plane (the 16-bit engines' head, gs_head1x1_wide_fwd) -- x_lo is never read.
+template <int DT, bool LO = true>
 __global__ __launch_bounds__(256) void head1x1_wide_split_kernel(const HeadSArgs a) {
     __shared__ __attribute__((aligned(16))) float wl[64 * 64];
     __shared__ float bl[64], scl[64], shl[64];
@@ -640,8 +641,11 @@ __global__ __launch_bounds__(256) void head1x1_wide_split_kernel(const HeadSArgs
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float v8[8];
-            join8<DT>(*reinterpret_cast<const uint4*>(a.x_hi + (int64_t)m * 64 + j * 8),
-                      *reinterpret_cast<const uint4*>(a.x_lo + (int64_t)m * 64 + j * 8), v8);
+            if constexpr (LO)
+                join8<DT>(*reinterpret_cast<const uint4*>(a.x_hi + (int64_t)m * 64 + j * 8),
+                          *reinterpret_cast<const uint4*>(a.x_lo + (int64_t)m * 64 + j * 8), v8);
+            else
+                unpack8<DT>(*reinterpret_cast<const uint4*>(a.x_hi + (int64_t)m * 64 + j * 8), v8);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 float t = v8[i];
@@ -930,5 +934,23 @@ static int head1x1_split_impl(const void* x_hi, const void* x_lo, const float* s
     if (dtype == GS_F16) head1x1_split_kernel<GS_F16><<<(int)hb, 256, 0, s>>>(a);
     else head1x1_split_kernel<GS_BF16><<<(int)hb, 256, 0, s>>>(a);
     GS_CHECK_LAUNCH("gs_head1x1_fwd_split");
+    return GS_OK;
+}
+
+// OutConv on ONE dense 16-bit plane [N,H,W,64] (the 16-bit engines): the wide kernel without its lo plane, every class in one launch
+extern "C" int gs_head1x1_wide_fwd(const void* x, const float* w, const float* bias, float* y, int N, int H, int W, int ncls,
+                                   int dtype, void* stream) {
+    GS_CHECK_ARG(x && w && y && N > 0 && H > 0 && W > 0, "gs_head1x1_wide_fwd: bad arguments");
+    GS_CHECK_ARG(ncls >= 1 && ncls <= 64, "gs_head1x1_wide_fwd: ncls=%d must be 1..64", ncls);
+    GS_CHECK_ARG(((uintptr_t)x & 15) == 0, "gs_head1x1_wide_fwd: x must be 16-byte aligned");
+    GS_CHECK_ARG((int64_t)N * H * W + 8192 * 256 < 2147483647LL, "gs_head1x1_wide_fwd: too many pixels");
+    GS_CHECK_ARG(dtype == GS_F16 || dtype == GS_BF16, "gs_head1x1_wide_fwd: bad dtype");
+    HeadSArgs a{(const unsigned short*)x, nullptr, w, bias, y, N, H * W, ncls};
+    int64_t wb = cdiv64((int64_t)N * H * W, 256);
+    if (wb > 8192) wb = 8192;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == GS_F16) head1x1_wide_split_kernel<GS_F16, false><<<(int)wb, 256, 0, s>>>(a);
+    else head1x1_wide_split_kernel<GS_BF16, false><<<(int)wb, 256, 0, s>>>(a);
+    GS_CHECK_LAUNCH("gs_head1x1_wide_fwd");
     return GS_OK;
 }

@@ -1451,6 +1451,42 @@ def head1x1_fwd_split(x_hi, x_lo, w, bias, y):
               _stream())
 
 
+def head1x1_wide_fwd(x, w, bias, y):
+    """OutConv 1x1 on ONE dense 16-bit plane [N,H,W,64] -> fp32 NCHW logits, 1..64 classes in one launch (the 16-bit engines' head)."""
+    _dev(x)
+    _f32(w, "w"); _f32(bias, "bias"); _f32(y, "y")
+    N, H, W, Cin = x.shape
+    ncls = y.shape[1]
+    if (Cin != 64 or not x.is_contiguous() or not y.is_contiguous() or tuple(y.shape) != (N, ncls, H, W) or not 1 <= ncls <= 64
+            or w.numel() != ncls * 64 or (bias is not None and bias.numel() != ncls)):
+        raise ValueError("head1x1_wide_fwd: x [N,H,W,64] dense, logits [N,ncls,H,W] with 1..64 classes, w [ncls,64], bias [ncls]")
+    _lib.call("gs_head1x1_wide_fwd", _p(x), _p(w), _p(bias), _p(y), N, H, W, ncls, dt_code(x), _stream())
+
+
+def head1x1_wide_bwd(z, w, dl, dz, dw, db, gscale=1.0):
+    """Backward of the pointwise head with 1..64 classes: dl fp32 [N,ncls,H,W] -> dz dense [N,H,W,64] 16-bit (one launch; None: not
+    formed) and dw [ncls,64] / db [ncls] fp32 += gscale * their sums (per-block slabs, ordered reduction; both None: not formed).
+    z: the head's stored 16-bit input [N,H,W,64] (None when dw is None)."""
+    _dev(dl)
+    _f32(w, "w"); _f32(dl, "dl"); _f32(dw, "dw"); _f32(db, "db")
+    ref = z if z is not None else dz
+    if ref is None or dl.dim() != 4:
+        raise ValueError("head1x1_wide_bwd: needs z or dz, and dl [N,ncls,H,W]")
+    N, H, W, Cin = ref.shape
+    ncls = dl.shape[1]
+    if (Cin != 64 or tuple(dl.shape) != (N, ncls, H, W) or not dl.is_contiguous() or not 1 <= ncls <= 64 or w.numel() != ncls * 64
+            or any(t is not None and (tuple(t.shape) != (N, H, W, 64) or not t.is_contiguous() or t.dtype != ref.dtype) for t in (z, dz))
+            or (dw is None) != (db is None) or (dw is None and dz is None) or (dw is not None and z is None)
+            or (dw is not None and (dw.numel() != ncls * 64 or db.numel() != ncls or not dw.is_contiguous() or not db.is_contiguous()))):
+        raise ValueError("head1x1_wide_bwd: z / dz [N,H,W,64] dense of one 16-bit dtype, dl [N,ncls,H,W] with 1..64 classes, w [ncls,64], "
+                         "dw [ncls,64] and db [ncls] together (with z) or both None")
+    ws = None
+    if dw is not None:
+        ws = torch.empty(int(_lib.load().gs_head1x1_wide_bwd_ws_floats(N, H, W, ncls)), dtype=torch.float32, device=dl.device)
+    _lib.call("gs_head1x1_wide_bwd", _p(z), _p(w), _p(dl), _p(dz), _p(dw), _p(db), _p(ws), N, H, W, ncls, float(gscale),
+              dt_code(ref), _stream())
+
+
 # ---------------------------------------------------------------------------- "q" stages: FP8 correction segment of the pair forward
 # (include/gsseg.h, csrc/common.hpp): the lo plane of a pair travels as a Q PLANE -- per 32 channels 64 bytes [lo8 | hi8] of e4m3 --
 # and a conv stage runs x_hi.w_hi on the 16-bit MFMA plus ONE block-scaled e4m3 segment for x_lo.w_hi + x_hi.w_lo.

@@ -567,8 +567,12 @@ class UNetEngine:
         elif net.n_classes <= 4:
             ops.conv_smallcout_fwd(inp, params["outc.conv.weight"].detach().contiguous(),
                                    params["outc.conv.bias"].detach(), logits)
+        elif net.n_classes <= 64:
+            # 5..64 classes: every class in one launch of the thread-per-pixel head kernel on the single 16-bit plane
+            ops.head1x1_wide_fwd(inp, params["outc.conv.weight"].detach().reshape(net.n_classes, 64).contiguous(),
+                                 params["outc.conv.bias"].detach(), logits)
         else:
-            # more than four classes (the reference takes any): the pointwise head kernel in groups of four output channels
+            # more than 64 classes (the reference takes any): the pointwise head kernel in groups of four output channels
             wo, bo = params["outc.conv.weight"].detach(), params["outc.conv.bias"].detach()
             for g0 in range(0, net.n_classes, 4):
                 g1 = min(g0 + 4, net.n_classes)
@@ -1128,8 +1132,12 @@ class UNetEngine:
             dz = None
             if z_last is not None:
                 ops.conv_smallcout_bwd(z_last, wout_c, dl, None, dwo, dbo, gscale=inv_s)
-        elif wout.shape[0] > 4:
-            # more than four classes: the head's backward in groups of four output channels, data gradients summed in fp32
+        elif 4 < wout.shape[0] <= 64:
+            # 5..64 classes: ONE data-gradient launch (the class sum in fp32, rounded once) and one weight-gradient launch
+            dz = empty(N, H, W, 64)
+            ops.head1x1_wide_bwd(z_last, wout_c.reshape(wout.shape[0], 64), dl, dz, dwo, dbo, gscale=inv_s)
+        elif wout.shape[0] > 64:
+            # more than 64 classes (16-bit engine only): groups of four output channels, data gradients summed in fp32
             dzs = torch.zeros((N, H, W, 64), dtype=torch.float32, device=dev)
             for g0 in range(0, wout.shape[0], 4):
                 g1 = min(g0 + 4, wout.shape[0])

@@ -137,6 +137,11 @@ class UNet3DEngine:
         self.grad_fetch = None
 
     # ------------------------------------------------------------------------------------------------
+    def _check_classes(self):
+        """the head kernels (forward, backward) take up to 64 classes; the reference takes any (GenSeg-3D/UNet3D/unet3d.py:89-126)"""
+        if self.net.s_block1.conv3.out_channels > 64:
+            raise NotImplementedError(f"UNet3D: the head kernels take up to 64 classes (got {self.net.s_block1.conv3.out_channels})")
+
     def forward(self, x, training, need_grad):
         net, tdt = self.net, self.tdt
         if not x.is_cuda:
@@ -146,6 +151,7 @@ class UNet3DEngine:
         NB, _, D0, H0, W0 = x.shape
         if D0 % 8 or H0 % 8 or W0 % 8:
             raise ValueError("volume dims must be multiples of 8 (three 2x2x2 poolings, no padding in the reference)")
+        self._check_classes()                              # both engines: refused here, before any launch and before "auto" falls back
         if self.plan is not None:
             if self.auto:
                 why = None
@@ -310,10 +316,13 @@ class UNet3DEngine:
             cur, ccur = z2, cmid
         head = net.s_block1.conv3
         ncls = head.out_channels
-        if ncls > 4:
-            raise NotImplementedError("num_classes above 4 is not supported by the direct head kernel")
         l2d = empty(NB * D0, ncls, H0, W0, dtype=torch.float32)
-        ops.conv_smallcout_fwd(cur, head.weight.detach().reshape(ncls, ccur, 1, 1).contiguous(), head.bias.detach(), l2d)
+        if ncls > 4:                                       # 5..64 classes: every class in one launch (_check_classes refused more)
+            if ccur != 64:
+                raise NotImplementedError("the pointwise head kernel for more than four classes reads 64 channels")
+            ops.head1x1_wide_fwd(cur, head.weight.detach().reshape(ncls, ccur).contiguous(), head.bias.detach(), l2d)
+        else:
+            ops.conv_smallcout_fwd(cur, head.weight.detach().reshape(ncls, ccur, 1, 1).contiguous(), head.bias.detach(), l2d)
         logits = l2d.view(NB, D0, ncls, H0, W0).permute(0, 2, 1, 3, 4).contiguous()
         ctx = None
         if need_grad:
@@ -360,8 +369,7 @@ class UNet3DEngine:
                 segs3d(plan[k + ".conv2"], sb.conv2.in_channels)
         if net.s_block1.conv2.out_channels != 64:
             raise NotImplementedError("pair forward: the pointwise head kernel reads 64 channels")
-        if net.num_classes > 4:
-            raise NotImplementedError("pair forward: num_classes above 4 is not supported by the head's backward kernel")
+        self._check_classes()
         cache[W0] = (lay, plan)
         return cache[W0]
 
@@ -686,8 +694,12 @@ class UNet3DEngine:
         dwo = torch.zeros((ncls, ctx["c_last"], 1, 1), dtype=torch.float32, device=dev)
         dbo = torch.zeros(ncls, dtype=torch.float32, device=dev)
         dz = empty(NB * D0, H0, W0, ctx["c_last"])
-        ops.conv_smallcout_bwd(ctx["z_last"], head.weight.detach().reshape(ncls, ctx["c_last"], 1, 1).contiguous(), dl,
-                               dz, dwo, dbo, gscale=inv_s)
+        if ncls > 4:                                       # 5..64 classes: one data-gradient launch, one weight-gradient launch
+            ops.head1x1_wide_bwd(ctx["z_last"], head.weight.detach().reshape(ncls, ctx["c_last"]).contiguous(), dl, dz, dwo, dbo,
+                                 gscale=inv_s)
+        else:
+            ops.conv_smallcout_bwd(ctx["z_last"], head.weight.detach().reshape(ncls, ctx["c_last"], 1, 1).contiguous(), dl,
+                                   dz, dwo, dbo, gscale=inv_s)
         emit(head.weight, dwo.view(head.weight.shape))
         emit(head.bias, dbo)
 
