@@ -202,6 +202,18 @@ __global__ __launch_bounds__(256) void bn_act_apply_kernel(const ApplyArgs a) {
 }
 
 // ---- backward ------------------------------------------------------------------------------------
+// a * b rounded to fp32 on its own, never contracted into a following add.  A consistency choice, not a correction: the
+// gradient with respect to the pre-activation, g * act'(v), is formed by the reduce and by the apply, plain and pooled, and all
+// of them should see the SAME fp32 number.  Left to the compiler, some of them accumulate fma(g, slope, s) (the unrounded
+// product, the more accurate sum) and others add the rounded product, so sums over the same operands differ in their last
+// bits from one variant to the next.  The file is built with -ffp-contract=fast, under which `#pragma clang fp contract(off)`
+// is disregarded, hence the opaque instruction.  Only LeakyReLU's 0.2 gives a product that rounds: see RN below.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+    float r;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
 struct BwdArgs {
     const unsigned short* y;
     const unsigned short* dza;
@@ -232,9 +244,13 @@ struct BwdArgs {
 // `switch` of act_fwd/act_grad costs a scalar branch per element and held these kernels at ~3 TB/s.
 // EXTRA: the second dense source (dzb) and / or the dropout keep-mask are present (Pix2Pix); without them their loads and
 // registers are compiled out (145-164 VGPRs otherwise: three waves per SIMD)
-template <int DT, bool POOL, bool APPLY, bool GENERIC, int HEAD = 0, bool EXTRA = true>   // HEAD: 0 = tensor sources; 2 / 4 = a head of <= 2 / 4 outputs
+// RN: a LeakyReLU is involved, the one slope whose product rounds: g * act'(v) goes through mul_rn.  g * 0 and g * 1 are exact
+// however they are fused, so the identity / ReLU launches (every launch of the U-Nets) take RN = false and pay nothing for it.
+template <int DT, bool POOL, bool APPLY, bool GENERIC, int HEAD = 0, bool EXTRA = true, bool RN = false>   // HEAD: 0 = tensor sources; 2 / 4 = a head of <= 2 / 4 outputs
 __global__ __launch_bounds__(256) void bn_act_bwd_kernel(const BwdArgs a) {
     static_assert(!HEAD || (!POOL && !GENERIC), "the head source: plain pixels, slope-family activation");
+    static_assert(!(RN && GENERIC), "the rounded slope product belongs to the slope family");
+    auto mul_g = [&](float g, float d) __attribute__((always_inline)) { return RN ? mul_rn(g, d) : g * d; };
     constexpr int NH = HEAD ? HEAD : 1;
     constexpr int HEAD_CHUNK = 2048;                        // pixels whose logit gradients are staged in LDS at a time
     __shared__ float hdl[HEAD ? NH * HEAD_CHUNK : 1];
@@ -348,7 +364,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_kernel(const BwdArgs a) {
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
                         const float v = yv[i] * sc[i] + sh[i];
-                        const float gh = g[i] * grad_a(v) + ((EXTRA && a.dzb) ? gb[i] * grad_b(v) : 0.f);
+                        const float gh = mul_g(g[i], grad_a(v)) + ((EXTRA && a.dzb) ? mul_g(gb[i], grad_b(v)) : 0.f);
                         const float xh = (yv[i] - mu[i]) * is[i];
                         if (APPLY) out[i] = a.bn ? sc[i] * (gh - k1[i] - xh * k2[i]) : gh;
                         else { s1[i] += gh; s2[i] += gh * xh; }
@@ -415,7 +431,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_kernel(const BwdArgs a) {
                     for (int i = 0; i < 8; ++i) {
                         const float gz = g[i] + (amax[i] == k ? gp[i] : 0.f);
                         const float v = yv[k][i] * sc[i] + sh[i];
-                        const float gh = gz * grad_a(v);
+                        const float gh = mul_g(gz, grad_a(v));
                         const float xh = (yv[k][i] - mu[i]) * is[i];
                         if (APPLY) out[i] = a.bn ? sc[i] * (gh - k1[i] - xh * k2[i]) : gh;
                         else { s1[i] += gh; s2[i] += gh * xh; }
@@ -680,32 +696,35 @@ static int launch_bwd(const BwdArgs& a0, bool apply, int dtype, hipStream_t s, i
     const int ntiles = (int)cdiv64(units, a.tile_units);
     if (ntiles_out) *ntiles_out = ntiles;
     const bool generic = a.act == GS_ACT_TANH || (a.dzb && a.act_b == GS_ACT_TANH);
-#define LAUNCH(DT, G)                                                                                   \
+    const bool leaky = !generic && (a.act == GS_ACT_LEAKY02 || (a.dzb && a.act_b == GS_ACT_LEAKY02));      // see RN
+#define LAUNCH(DT, G, R)                                                                                \
     do {                                                                                                \
         if (pool) {                                                                                     \
-            if (apply) bn_act_bwd_kernel<DT, true, true, G><<<ntiles, 256, 0, s>>>(a);                  \
-            else bn_act_bwd_kernel<DT, true, false, G><<<ntiles, 256, 0, s>>>(a);                       \
+            if (apply) bn_act_bwd_kernel<DT, true, true, G, 0, true, R><<<ntiles, 256, 0, s>>>(a);      \
+            else bn_act_bwd_kernel<DT, true, false, G, 0, true, R><<<ntiles, 256, 0, s>>>(a);           \
         } else if (a.dzb != nullptr || a.keep != nullptr) {                                             \
-            if (apply) bn_act_bwd_kernel<DT, false, true, G><<<ntiles, 256, 0, s>>>(a);                 \
-            else bn_act_bwd_kernel<DT, false, false, G><<<ntiles, 256, 0, s>>>(a);                      \
+            if (apply) bn_act_bwd_kernel<DT, false, true, G, 0, true, R><<<ntiles, 256, 0, s>>>(a);     \
+            else bn_act_bwd_kernel<DT, false, false, G, 0, true, R><<<ntiles, 256, 0, s>>>(a);          \
         } else {                                                                                        \
-            if (apply) bn_act_bwd_kernel<DT, false, true, G, 0, false><<<ntiles, 256, 0, s>>>(a);       \
-            else bn_act_bwd_kernel<DT, false, false, G, 0, false><<<ntiles, 256, 0, s>>>(a);            \
+            if (apply) bn_act_bwd_kernel<DT, false, true, G, 0, false, R><<<ntiles, 256, 0, s>>>(a);    \
+            else bn_act_bwd_kernel<DT, false, false, G, 0, false, R><<<ntiles, 256, 0, s>>>(a);         \
         }                                                                                               \
     } while (0)
     if (a.head_dl != nullptr) {                            // the head source: plain pixels, slope-family activation (host checks)
-#define LAUNCH_HEAD(DT, NC)                                                                             \
+#define LAUNCH_HEAD(DT, NC, R)                                                                          \
     do {                                                                                                \
-        if (apply) bn_act_bwd_kernel<DT, false, true, false, NC, false><<<ntiles, 256, 0, s>>>(a);      \
-        else bn_act_bwd_kernel<DT, false, false, false, NC, false><<<ntiles, 256, 0, s>>>(a);           \
+        if (apply) bn_act_bwd_kernel<DT, false, true, false, NC, false, R><<<ntiles, 256, 0, s>>>(a);   \
+        else bn_act_bwd_kernel<DT, false, false, false, NC, false, R><<<ntiles, 256, 0, s>>>(a);        \
     } while (0)
-        if (dtype == GS_F16) { if (a.head_n <= 2) LAUNCH_HEAD(GS_F16, 2); else LAUNCH_HEAD(GS_F16, 4); }
-        else { if (a.head_n <= 2) LAUNCH_HEAD(GS_BF16, 2); else LAUNCH_HEAD(GS_BF16, 4); }
+#define LAUNCH_HEAD_N(DT, R) do { if (a.head_n <= 2) LAUNCH_HEAD(DT, 2, R); else LAUNCH_HEAD(DT, 4, R); } while (0)
+        if (dtype == GS_F16) { if (leaky) LAUNCH_HEAD_N(GS_F16, true); else LAUNCH_HEAD_N(GS_F16, false); }
+        else { if (leaky) LAUNCH_HEAD_N(GS_BF16, true); else LAUNCH_HEAD_N(GS_BF16, false); }
+#undef LAUNCH_HEAD_N
 #undef LAUNCH_HEAD
         return 0;
     }
-    if (dtype == GS_F16) { if (generic) LAUNCH(GS_F16, true); else LAUNCH(GS_F16, false); }
-    else { if (generic) LAUNCH(GS_BF16, true); else LAUNCH(GS_BF16, false); }
+    if (dtype == GS_F16) { if (generic) LAUNCH(GS_F16, true, false); else if (leaky) LAUNCH(GS_F16, false, true); else LAUNCH(GS_F16, false, false); }
+    else { if (generic) LAUNCH(GS_BF16, true, false); else if (leaky) LAUNCH(GS_BF16, false, true); else LAUNCH(GS_BF16, false, false); }
 #undef LAUNCH
     return 0;
 }

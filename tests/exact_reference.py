@@ -53,10 +53,10 @@ def draw(g, vset: str, kind: str, shape, d: float = None) -> torch.Tensor:
 
 def density(pixels: int, products: int) -> float:
     """T(d) for a case whose per-channel sums over `pixels` outputs of `products` products each are checked: every product is
-    +-1 with probability d^2, so E[sum y^2] = pixels * products * d^2; the largest d in 1/2 .. 1/32 that keeps this expectation
+    +-1 with probability d^2, so E[sum y^2] = pixels * products * d^2; the largest d in 1/2 .. 1/64 that keeps this expectation
     under 2^23 (a factor 2 for the spread across channels).  tests/test_exact_reference_cpu.py proves each choice on the
     reference."""
-    for k in (1, 2, 3, 4, 5):
+    for k in (1, 2, 3, 4, 5, 6):
         d = 0.5 ** k
         if pixels * products * d * d < LIMIT / 2:
             return d
@@ -75,13 +75,18 @@ def require_products(n_products: int, a: torch.Tensor, b: torch.Tensor, what: st
     assert bound < LIMIT, f"{what}: {n_products} products x {float(a.abs().max())} x {float(b.abs().max())} = {bound} >= 2^24"
 
 
-def require_channel_sums(y: torch.Tensor, what: str = ""):
+def require_channel_sums(y: torch.Tensor, what: str = "", squares: bool = True):
     """y [N, C, ...]: per channel, the sums over all pixels of |y| and y^2 stay below 2^24 (any sub-sum a kernel forms per
-    tile, block or split is then exact too).  Returns the exact sums (sum y, sum y^2) in fp64."""
+    tile, block or split is then exact too).  Returns the exact sums (sum y, sum y^2) in fp64.  squares=False: only the sum
+    of |y| is part of the case (sum y^2 is neither bounded nor returned)."""
     yd = y.double()
     dims = [0] + list(range(2, y.dim()))
+    sa = float(yd.abs().sum(dims).max())
+    if not squares:
+        assert sa < LIMIT, f"{what}: max sum |y| = {sa} >= 2^24"
+        return yd.sum(dims), None
     s2 = (yd * yd).sum(dims)
-    assert float(yd.abs().sum(dims).max()) < LIMIT and float(s2.max()) < LIMIT, f"{what}: max sum y^2 = {float(s2.max())} >= 2^24"
+    assert sa < LIMIT and float(s2.max()) < LIMIT, f"{what}: max sum y^2 = {float(s2.max())} >= 2^24"
     return yd.sum(dims), s2
 
 
@@ -673,3 +678,461 @@ def image_wgrad_build(case):
     wm = torch.zeros(Cin, 1, 8, 8)
     _, (_, dwm) = autograd(lambda a, c: F.conv_transpose2d(a, c, None, stride=2, padding=3), (x, wm), du, wrt=[1])
     return {"x": x, "du": du, "dwm": merged_to_classes(dwm)}
+
+
+# ------------------------------------------------------------------------------------------------ G: BatchNorm / activation
+# csrc/bn.hip stated without tiles or lanes, in fp64:
+#   forward   z = act(y * scale + shift) [* (keep ? keep_scale : 0)], rounded ONCE to the 16-bit dtype; the pooled output is
+#             the max over the ROUNDED z of every complete 2x2 window
+#   backward  v = y * scale + shift;  gh = (keep * dz_a + dzp routed to the first maximum of the rounded z) * act'(v) + dz_b * act_b'(v)
+#             s1 = sum gh, s2 = sum gh * xh with xh = (y - mean) * invstd;  dy = bn ? scale * (gh - c1 - xh * c2) : gh
+#             act'(0): ReLU 0, LeakyReLU 0.2 (v > 0 ? 1 : slope)
+# Operands: y integers of range S (times 5 under LeakyReLU), mean small integers, invstd and |gamma| powers of two (gamma
+# negative on every third channel), shift integers (near 300 and 2100 on a quarter of the channels each, so that z rounds in
+# bf16 and in fp16 and the rounding makes ties), c1 / c2 multiples of 1/4, keep bytes from {0, 1, 255}, keep_scale 2.
+KEEP_SCALE = 2.0
+BN_LARGE = 32768                    # pixels from which the gradients are drawn sparse, T(d) times the multiplier
+BN_MUTANTS = ("relu0", "last", "keep_on_b", "slope_b", "unrounded", "drop63")
+
+
+def require_dyadic(t: torch.Tensor, what: str = "", max_bits: int = 8) -> int:
+    """every element is a multiple of 2^-k for a k <= max_bits and |t| * 2^k < 2^24: t is an fp32 number.  Returns that k."""
+    td = t.double()
+    for k in range(max_bits + 1):
+        s = td * 2.0 ** k
+        if torch.equal(s, s.round()):
+            assert float(s.abs().max()) < LIMIT if s.numel() else True, f"{what}: {float(s.abs().max())} * 2^-{k} has more than 24 bits"
+            return k
+    raise AssertionError(f"{what}: not a multiple of 2^-{max_bits}")
+
+
+def require_fifths(*tensors):
+    """LeakyReLU(0.2) operands: x / 5 is a dyadic number and float32(x) * float32(0.2) is exactly that number (true for every
+    multiple of 5, or of 5 * 2^-k, in the ranges used here; false for general integers), so the slope needs no allowance."""
+    slope = torch.tensor(0.2, dtype=torch.float32)
+    for t in tensors:
+        q = t.double() / 5
+        require_dyadic(q, "x / 5", 4)
+        assert torch.equal((t.float() * slope).double(), q), "float32(x) * float32(0.2) is not the exact x / 5"
+
+
+def act_fwd64(v: torch.Tensor, act: str) -> torch.Tensor:
+    if act == "none":
+        return v
+    return torch.where(v > 0, v, torch.zeros_like(v) if act == "relu" else v / 5)
+
+
+def act_bwd64(g: torch.Tensor, v: torch.Tensor, act: str, relu_at_0: float = 0.0) -> torch.Tensor:
+    """g * act'(v) with act'(0) = 0 for ReLU (relu_at_0: the mutant's value) and 0.2 for LeakyReLU"""
+    if act == "none":
+        return g
+    if act == "relu":
+        return torch.where(v > 0, g, torch.where(v == 0, g * relu_at_0, torch.zeros_like(g)))
+    return torch.where(v > 0, g, g / 5)
+
+
+def route_pool2(zr: torch.Tensor, dzp: torch.Tensor, last: bool = False):
+    """dzp [N, C, H/2, W/2] routed to the first (last: the mutant) maximum of every complete 2x2 window of zr [N, C, H, W] in
+    scan order (0,0) (0,1) (1,0) (1,1).  Returns the routed gradient [N, C, H, W] and the share of windows with a tied maximum."""
+    N, C, H, W = zr.shape
+    PH, PW = H // 2, W // 2
+    win = zr[:, :, :2 * PH, :2 * PW].reshape(N, C, PH, 2, PW, 2).permute(0, 1, 2, 4, 3, 5).reshape(N, C, PH, PW, 4)
+    is_max = win == win.amax(-1, keepdim=True) if win.numel() else torch.zeros_like(win, dtype=torch.bool)
+    order = is_max.flip(-1) if last else is_max
+    pick = order & (order.cumsum(-1) == 1)
+    if last:
+        pick = pick.flip(-1)
+    routed = pick * dzp.double().unsqueeze(-1)
+    out = torch.zeros_like(zr, dtype=torch.float64)
+    out[:, :, :2 * PH, :2 * PW] = routed.reshape(N, C, PH, PW, 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(N, C, 2 * PH, 2 * PW)
+    ties = float((is_max.sum(-1) > 1).double().mean()) if win.numel() else 0.0
+    return out, ties
+
+
+def _bnv(act="relu", dza="slice", dzb=None, keep=False, bn=True, ident=False):
+    return dict(act=act, dza=dza, dzb=dzb, keep=keep, bn=bn, ident=ident)
+
+
+# dza: "slice" (channels [C, 2C) of a 2C-wide buffer, poison outside), "dense" or None; dzb: None or its activation act_b
+BN_VARIANTS = {
+    "relu": _bnv(),
+    "none_dense": _bnv(act="none", dza="dense"),
+    "leaky": _bnv(act="leaky"),
+    "b_only": _bnv(dza=None, dzb="none"),
+    "b_leaky": _bnv(dza="dense", dzb="leaky"),                    # the Pix2Pix down path
+    "keep_b": _bnv(keep=True, dzb="none"),                        # the mask must not touch dz_b
+    "keep_b_leaky": _bnv(dza="dense", keep=True, dzb="leaky"),
+    "keep_bn0": _bnv(act="none", dza="dense", keep=True, bn=False),
+    "ident": _bnv(dza="dense", bn=False, ident=True),             # scale / shift NULL
+    "leaky_bn0": _bnv(act="leaky", dza="dense", bn=False),
+    "pool_only": _bnv(dza=None),                                  # pooled shapes: dzp is the only source
+}
+_BN_PLAIN = [v for v in BN_VARIANTS if v != "pool_only"]
+_BN_POOLED = [v for v, s in BN_VARIANTS.items() if s["dzb"] is None and not s["keep"]]
+BN_SHAPES = [(1, 1, 1, 8), (2, 9, 7, 24), (2, 33, 31, 72), (2, 64, 64, 64), (1, 5, 5, 1024), (1, 4, 4, 2048), (1, 192, 192, 8),
+             (3, 160, 150, 8)]
+BN_FULL_SHAPES = [(2, 9, 7, 24), (2, 64, 64, 64), (3, 160, 150, 8)]             # every variant
+BN_POOLED_SHAPES = [(2, 9, 7, 64), (1, 65, 33, 128), (2, 64, 64, 64)]            # every variant that is legal with a pool
+BN_TWO_STAGE_SHAPES = [(1, 192, 192, 8), (3, 160, 150, 8)]                      # more than 512 tiles (576 and 1015): gs_bn_bwd_coeffs in two stages
+# (shape, pooled, variant): the other plain shapes run "relu" and one more variant each, in turn
+BN_CASES = ([(s, False, v) for s in BN_FULL_SHAPES for v in _BN_PLAIN]
+            + [(s, False, v) for i, s in enumerate(x for x in BN_SHAPES if x not in BN_FULL_SHAPES)
+               for v in ("relu", [x for x in _BN_PLAIN if x != "relu"][(2 * i) % (len(_BN_PLAIN) - 1)])]
+            + [(s, True, v) for s in BN_POOLED_SHAPES for v in _BN_POOLED])
+BN_FWD_ONLY_CASES = [((2, 96, 96, 512), False, "leaky"), ((2, 96, 96, 512), False, "keep_bn0")]
+BN_HEAD_CASES = [(2, 18, 22, 64, 2), (3, 45, 53, 64, 1), (2, 40, 40, 32, 4)]
+BN_HEAD_TWO_CHUNKS = (1, 1472, 1472, 8, 3)                    # fp16 only: 2116 pixels per tile, a second LDS chunk of 68
+BN_REV_CASES = [((2, 9, 7, 24), False, "keep_b_leaky"), ((2, 33, 31, 72), False, "relu"), ((2, 9, 7, 64), True, "leaky")]
+
+
+def _bn_density(pixels, act, fan=1):
+    """gradient density of a case.  Target: per channel, sum over the pixels of |gh| * |xh| in units of its last bit < 2^24 (the
+    s2 condition of _bn_finish; s1 is the weaker one).  Dense below BN_LARGE weighted pixels, density() of them from there on:
+      weight = 4 * fan   act = LeakyReLU: y and the gradients both carry the factor 5, so the products |gh * xh| are larger
+      weight = fan / 4   otherwise (a LeakyReLU on act_b alone puts the 5 on the gradients only; y keeps its range)
+      fan                1 for tensor sources; the head source sums `classes` products with |w_head| up to 4.
+    The weights are rough on purpose: density() moves in steps of 4 in the sum it bounds.
+    This only picks a starting point: _bn_finish proves every choice on the operands with require_channel_sums, and a choice
+    that were too dense fails there, on the CPU."""
+    weight = 4 * fan if act == "leaky" else max(1, fan // 4)
+    return density(pixels * weight, 2048) if pixels * weight >= BN_LARGE else None
+
+
+def bn_pixel63(shape, pooled=False):
+    """(n, y, x) of pixel 63 of an [N, H, W, C] tensor -- the last of the first 64-pixel run -- or of its 2x2 window"""
+    N, H, W, C = shape
+    n, rem = divmod(63, H * W)
+    yy, xx = divmod(rem, W)
+    return (n, yy // 2, xx // 2) if pooled else (n, yy, xx)
+
+
+def _at63(shape, pooled=False):
+    """index of channel 0 of pixel 63 (of its window) in an NCHW operand"""
+    n, yy, xx = bn_pixel63(shape, pooled)
+    return (n, 0, yy, xx)
+
+
+def bn_id(case):
+    shape, pooled, v = case
+    return "x".join(str(i) for i in shape) + ("-pool-" if pooled else "-") + v
+
+
+def _bn_operands(g, shape, act, ident):
+    """y and the per-channel coefficients of one case; zeros of v planted on the channels c % 4 == 0 (|scale| = 1 there)"""
+    N, H, W, C = shape
+    m = 5.0 if act == "leaky" else 1.0
+    c = torch.arange(C)
+    invstd = 2.0 ** torch.randint(-1, 2, (C,), generator=g).double()
+    gmag = torch.where(c % 4 == 0, 1.0 / invstd, 2.0 ** torch.randint(-1, 2, (C,), generator=g).double())
+    sign = torch.where(c % 3 == 1, -1.0, 1.0).double()
+    small = torch.randint(-2, 3, (C,), generator=g).double()
+    shift = (small + torch.where(c % 4 == 1, 300.0, 0.0) + torch.where(c % 4 == 2, 2100.0, 0.0)) * m
+    scale = sign * gmag * invstd
+    mean = torch.randint(-2, 3, (C,), generator=g).double()
+    c1 = torch.randint(-16, 17, (C,), generator=g).double() / 4
+    c2 = torch.randint(-16, 17, (C,), generator=g).double() / 4
+    y = tied_values(g, (N, C, H, W), tuple(range(-8, 9))).double() * m
+    if not ident:
+        plant = (torch.rand((N, C, H, W), generator=g) < 0.125)
+        plant[0, :, 0, 0] = True
+        plant &= (c % 4 == 0).view(1, -1, 1, 1)
+        y = torch.where(plant, (-shift * sign).view(1, -1, 1, 1).expand_as(y), y)
+    if N * H * W >= 64:
+        y[_at63(shape)] = 8.0 * m           # pixel 63, channel 0 (scale +1): v > 0, the largest z of its window
+    require_integers(y, mean)
+    assert torch.equal(shift, shift.round())
+    for t in (invstd, gmag):
+        for s in t.unique().tolist():
+            require_pow2(s)
+    assert float(c1.abs().max()) <= 4 and float(c2.abs().max()) <= 4 and require_dyadic(torch.cat([c1, c2])) <= 2
+    out = {"y": y.float(), "mean": mean.float(), "invstd": invstd.float(), "c1": c1.float(), "c2": c2.float(),
+           "scale": None if ident else scale.float(), "shift": None if ident else shift.float(), "gamma_negative": int((sign < 0).sum())}
+    return out
+
+
+def _col(t, C, default):
+    return (torch.full((C,), default, dtype=torch.float64) if t is None else t.double()).view(1, -1, 1, 1)
+
+
+def _bn_finish(c, what):
+    """the conditions every intermediate of the kernel has to meet, asserted on the operands of case c (in place: adds the
+    shares of v == 0 and of tied windows)"""
+    y = c["y"].double()
+    C = y.shape[1]
+    scale, shift, mean, invstd = _col(c["scale"], C, 1.0), _col(c["shift"], C, 0.0), _col(c["mean"], C, 0.0), _col(c["invstd"], C, 1.0)
+    v = y * scale + shift
+    require_dyadic(v, what + " v")
+    xh = (y - mean) * invstd
+    kx = require_dyadic(xh, what + " xh")
+    leaky = "leaky" in (c["act"], c["act_b"] if c["dzb"] is not None else None)
+    grads = [t for t in (c["dza"], c["dzb"], c["dzp"]) if t is not None]
+    for t in grads:
+        require_dyadic(t, what + " gradient operand", 1)
+        assert float(t.abs().max()) <= 2560
+    if leaky:
+        require_fifths(*grads)
+    if c["act"] == "leaky":
+        require_fifths(c["y"], v)
+        if c["shift"] is not None:
+            require_fifths(c["shift"])
+    require_pow2(c["keep_scale"])
+    if c["keep"] is not None:
+        assert set(c["keep"].unique().tolist()) <= {0, 1, 255}
+    # |gh| <= keep_scale |dz_a| + |dz_b| + |dzp| at ONE pixel of its window: the channel totals of this bound (for s2: times |xh|,
+    # the routed part times the largest |xh| of the window) are exact, so every sub-sum a kernel forms is
+    bound = torch.zeros_like(y)
+    if c["dza"] is not None:
+        bound += c["dza"].double().abs() * (c["keep_scale"] if c["keep"] is not None else 1.0)
+    if c["dzb"] is not None:
+        bound += c["dzb"].double().abs()
+    b1, b2 = bound.clone(), bound * xh.abs()
+    if c["dzp"] is not None and c["dzp"].numel():
+        PH, PW = c["dzp"].shape[2:]
+        b1[:, :, 0:2 * PH:2, 0:2 * PW:2] += c["dzp"].double().abs()
+        b2[:, :, 0:2 * PH:2, 0:2 * PW:2] += c["dzp"].double().abs() * F.max_pool2d(xh.abs(), 2)
+    kg = require_dyadic(b1 / (5.0 if leaky else 1.0), what + " gh")
+    require_channel_sums(b1 * 2.0 ** kg, what + " s1", squares=False)
+    require_channel_sums(b2 * 2.0 ** (kg + kx), what + " s2", squares=False)
+    c["zero_share"] = float((v == 0).double().mean())
+    c["tie_share"] = route_pool2(act_fwd64(v, c["act"]), torch.zeros(1), False)[1] if c["pooled"] else 0.0
+    return c
+
+
+def bn_build(shape, pooled, vname):
+    """operands of one case of BN_CASES / BN_FWD_ONLY_CASES, NCHW on the CPU; bn_reference gives the expected values"""
+    N, H, W, C = shape
+    s = BN_VARIANTS[vname]
+    g = generator(("bn", tuple(shape), pooled, vname))
+    px = N * H * W
+    leaky = "leaky" in (s["act"], s["dzb"])
+    gm = 5.0 if leaky else 1.0
+    d = _bn_density(px, s["act"])
+
+    def grad(shp, pool=False):
+        t = (draw(g, "T", "a", shp, d) if d else draw(g, "S", "a", shp)) * gm
+        if t.numel():
+            t.view(-1)[0] = gm                   # a gradient on the planted v == 0 of pixel 0, channel 0
+        if px >= 64:
+            t[_at63(shape, pool)] = gm        # and on pixel 63 (its window), where v > 0
+        return t
+    c = _bn_operands(g, shape, s["act"], s["ident"])
+    c.update(act=s["act"], act_b=s["dzb"] or "none", bn=s["bn"], pooled=pooled, dza_kind=s["dza"], keep_scale=KEEP_SCALE, d=d,
+             dza=grad((N, C, H, W)) if s["dza"] else None, dzb=grad((N, C, H, W)) if s["dzb"] else None,
+             dzp=grad((N, C, H // 2, W // 2), True) if pooled else None, keep=None)
+    if s["keep"]:
+        assert not pooled
+        c["keep"] = torch.tensor([0, 1, 255], dtype=torch.uint8)[torch.randint(0, 3, (N, C, H, W), generator=g)]
+        if px >= 64:
+            c["keep"][_at63(shape)] = 255
+    return _bn_finish(c, bn_id((shape, pooled, vname)))
+
+
+def bn_head_build(case):
+    """the head source: dz_a[p][c] = sum_k dl[n][k][hw] * w_head[k][c] (fp32 in the kernel, never rounded to 16 bits), dl integer
+    (multiples of 5 under LeakyReLU, sparse on the large case), w_head powers of two on the even and small integers on the odd
+    channels; ReLU for 1 to 3 classes, LeakyReLU for 4"""
+    N, H, W, C, ncls = case
+    g = generator(("bn_head",) + tuple(case))
+    px = N * H * W
+    act = "leaky" if ncls == 4 else "relu"
+    gm = 5.0 if act == "leaky" else 1.0
+    d = _bn_density(px, act, 4 * ncls)
+    dl = (draw(g, "T", "a", (N, ncls, H, W), d) if d else draw(g, "S", "a", (N, ncls, H, W))) * gm
+    dl[0, :, 0, 0] = gm
+    dl[(bn_pixel63((N, H, W, C))[0], slice(None)) + bn_pixel63((N, H, W, C))[1:]] = gm
+    wp = (torch.randint(0, 2, (ncls, C), generator=g) * 2 - 1) * 2.0 ** torch.randint(-1, 2, (ncls, C), generator=g).double()
+    wi = draw(g, "S", "w", (ncls, C)).double()
+    wh = torch.where(torch.arange(C) % 2 == 0, wp, wi)
+    wh[:, 0] = 1.0
+    require_integers(dl)
+    require_dyadic(wh, "w_head", 1)
+    assert ncls * float(dl.abs().max()) * float(wh.abs().max()) * 2 < LIMIT        # every partial sum over k, in halves
+    dza = torch.einsum("nkhw,kc->nchw", dl.double(), wh)
+    c = _bn_operands(g, (N, H, W, C), act, False)
+    c.update(act=act, act_b="none", bn=True, pooled=False, dza_kind="head", keep_scale=KEEP_SCALE, d=d, dza=dza, dzb=None, dzp=None,
+             keep=None, dl=dl, w_head=wh.float(), ncls=ncls)
+    return _bn_finish(c, "head " + "x".join(str(i) for i in case))
+
+
+def bn_mutant_applies(c, mutant, dt=None) -> bool:
+    """whether `mutant` changes what case c asks of the kernel (otherwise it IS the reference there)"""
+    pixels = c["y"].shape[0] * c["y"].shape[2] * c["y"].shape[3]
+    return {"relu0": c["act"] == "relu" and (c["dza"] is not None or c["pooled"]),
+            "last": c["pooled"],
+            "keep_on_b": c["keep"] is not None and c["dzb"] is not None,
+            "slope_b": c["dzb"] is not None and c["act_b"] != c["act"],
+            # without scale / shift z = act(y) holds |y| <= 8 exactly in both dtypes: rounded and unrounded z are the same numbers
+            "unrounded": c["pooled"] and c["scale"] is not None,
+            "drop63": pixels >= 64}[mutant]
+
+
+def bn_reference(c, dt, mutant=None):
+    """fp64 expected values of case c for the 16-bit dtype dt: z, zp (forward), gh, s1, s2 (tile-free sums) and dy computed with
+    the c1 / c2 of the case.  mutant: one of BN_MUTANTS, a reference that is wrong in one stated way (the CPU test shows that the
+    comparer tells each from the reference)."""
+    assert mutant is None or mutant in BN_MUTANTS
+    y = c["y"].double()
+    N, C, H, W = y.shape
+    scale, shift, mean, invstd = _col(c["scale"], C, 1.0), _col(c["shift"], C, 0.0), _col(c["mean"], C, 0.0), _col(c["invstd"], C, 1.0)
+    v = y * scale + shift
+    z = act_fwd64(v, c["act"])
+    kf = None if c["keep"] is None else torch.where(c["keep"] != 0, c["keep_scale"], 0.0).double()
+    out = {"z": expect16(z if kf is None else z * kf, dt)}
+    g = torch.zeros_like(y)
+    if c["dza"] is not None:
+        g = c["dza"].double() if kf is None else c["dza"].double() * kf
+    if c["pooled"]:
+        zr = out["z"].double()
+        out["zp"] = F.max_pool2d(zr, 2).to(dt) if H >= 2 and W >= 2 else zr.new_zeros((N, C, H // 2, W // 2)).to(dt)
+        g = g + route_pool2(z if mutant == "unrounded" else zr, c["dzp"], last=(mutant == "last"))[0]
+    gh = act_bwd64(g, v, c["act"], 1.0 if mutant == "relu0" else 0.0)
+    if c["dzb"] is not None:
+        gb = c["dzb"].double()
+        if mutant == "keep_on_b":
+            gb = gb * kf
+        gh = gh + act_bwd64(gb, v, c["act"] if mutant == "slope_b" else c["act_b"])
+    if mutant == "drop63":
+        flat = gh.permute(0, 2, 3, 1).reshape(-1, C).clone()
+        flat[63] = 0                                        # the last pixel of the first 64-pixel run, every channel
+        gh = flat.view(N, H, W, C).permute(0, 3, 1, 2)
+    xh = (y - mean) * invstd
+    out["gh"] = gh
+    out["s1"], out["s2"] = gh.sum((0, 2, 3)), (gh * xh).sum((0, 2, 3))
+    out["dy"] = scale * (gh - _col(c["c1"], C, 0.0) - xh * _col(c["c2"], C, 0.0)) if c["bn"] else gh
+    return out
+
+
+def bn_fp32_shuffled(c, dt, seed):
+    """the backward of case c the way a kernel may form it: every elementwise step in fp32 (v, the slope product, the keep
+    factor, xh, the terms, dy), the sums over a random permutation of the pixels in runs of 64 summed in fp32, then the run sums
+    in fp32.  Equal to bn_reference bit for bit is what entitles the GPU test to zero tolerance."""
+    f = torch.float32
+    y = c["y"].to(f)
+    N, C, H, W = y.shape
+    col = lambda t, dflt: (torch.full((C,), dflt, dtype=f) if t is None else t.to(f)).view(1, -1, 1, 1)     # noqa: E731
+    scale, shift, mean, invstd = col(c["scale"], 1.0), col(c["shift"], 0.0), col(c["mean"], 0.0), col(c["invstd"], 1.0)
+    slope = {"none": 1.0, "relu": 0.0, "leaky": 0.2}
+    sa, sb = torch.tensor(slope[c["act"]], dtype=f), torch.tensor(slope[c["act_b"]], dtype=f)
+    one = torch.tensor(1.0, dtype=f)
+    v = y * scale + shift
+    g = torch.zeros_like(y)
+    if c["dza"] is not None:
+        g = c["dza"].to(f)
+        if c["keep"] is not None:
+            g = g * torch.where(c["keep"] != 0, c["keep_scale"], 0.0).to(f)
+    if c["pooled"]:
+        zr = torch.where(v > 0, v, v * sa).to(dt).double()
+        g = g + route_pool2(zr, c["dzp"])[0].to(f)
+    gh = g * torch.where(v > 0, one, sa)
+    if c["dzb"] is not None:
+        gh = gh + c["dzb"].to(f) * torch.where(v > 0, one, sb)
+    xh = (y - mean) * invstd
+    dy = scale * (gh - col(c["c1"], 0.0) - xh * col(c["c2"], 0.0)) if c["bn"] else gh
+    perm = torch.randperm(N * H * W, generator=torch.Generator().manual_seed(seed))
+    sums = []
+    for t in (gh, gh * xh):
+        rows = t.permute(0, 2, 3, 1).reshape(-1, C)[perm]
+        acc = torch.zeros(C, dtype=f)
+        for run in rows.split(64):
+            part = torch.zeros(C, dtype=f)
+            for r in run.split(16):
+                part = part + r.sum(0, dtype=f)
+            acc = acc + part
+        sums.append(acc)
+    assert v.dtype == gh.dtype == dy.dtype == sums[0].dtype == f
+    return {"gh": gh, "s1": sums[0], "s2": sums[1], "dy": dy}
+
+
+# ---- tanh (the Pix2Pix output layer): not exact; per element, the correctly rounded 16-bit value or its neighbour
+TANH_CASES = [((2, 9, 7, 24), False), ((2, 33, 31, 72), False), ((2, 9, 7, 64), True), ((1, 65, 33, 128), True)]     # (shape, pooled)
+TANH_NEIGHBOUR_SHARE = 0.01
+
+
+def tanh_build(shape, pooled):
+    """y multiples of 1/8 with |y| <= 1.5 (exact in both dtypes, with ties), integer dz; z = tanh(y), dy = dz * (1 - tanh(y)^2).
+    Why |y| <= 1.5: 1 - t^2 cancels, an error e of t becomes 2 t e / (1 - t^2) relative, at most 9 e here."""
+    N, H, W, C = shape
+    g = generator(("tanh", tuple(shape), pooled))
+    y = tied_values(g, (N, C, H, W), tuple(k / 8 for k in range(-12, 13)))
+    dz = draw(g, "S", "a", (N, C, H, W))
+    t = torch.tanh(y.double())
+    return {"y": y, "dz": dz, "z": t, "dy": dz.double() * (1 - t * t)}
+
+
+def ordered16(t: torch.Tensor) -> torch.Tensor:
+    """a 16-bit float tensor as integers whose order is the order of the values (+0 and -0 both 0): neighbours differ by 1"""
+    b = t.view(torch.int16).int()
+    return torch.where(b < 0, -(b & 0x7FFF), b)
+
+
+def neighbour16(got: torch.Tensor, ref64: torch.Tensor):
+    """(ok, share): ok marks the elements of `got` that are the 16-bit value nearest to the fp64 reference or adjacent to it;
+    share is the fraction that sit on the neighbour"""
+    want = ref64.to(got.dtype).to(got.device)
+    exact = got == want
+    ok = exact | ((ordered16(got) - ordered16(want)).abs() <= 1)
+    return ok, float((ok & ~exact).double().mean())
+
+
+# ---- gs_bn_finalize / gs_bn_eval_coeffs against numpy fp64: bounds from the count of fp32 roundings, see the GPU test
+BN_FINALIZE_C = (24, 64, 72)
+BN_FINALIZE_TILES = (1, 2, 512, 513, 1200)
+BN_EPS = 1e-5
+BN_MOMENTUM = 0.1
+# fp32 roundings on the way to each output of gs_bn_finalize, counted in the docstring of its GPU test
+BN_FINALIZE_ROUNDINGS = {"mean": 1, "invstd": 1, "scale": 2, "shift": 5, "rm": 3, "rv": 3}
+BN_EVAL_ROUNDINGS = {"mean": 0, "invstd": 3, "scale": 4, "shift": 6}
+
+
+def bn_finalize_build(C, ntiles, count_one=False):
+    """fp32 tile partials [ntiles][2][C] of `ntiles` tiles of 64 pixels (count_one: one tile of one pixel): channel 0 is constant
+    (its sum of squares one fp32 step BELOW count * value^2, so the variance comes out negative and must clamp at 0), channel 1 has
+    |mean| = 100 * std; gamma, beta and running statistics"""
+    import numpy as np
+    rng = np.random.default_rng(case_seed(("bn_finalize", C, ntiles, count_one)))
+    T = 1 if count_one else 64
+    mean = rng.uniform(-2, 2, C)
+    std = rng.uniform(0.5, 2, C)
+    mean[1], std[1] = 50.0, 0.5
+    tm = mean + std * rng.standard_normal((ntiles, C)) / np.sqrt(T)            # tile means
+    tv = std ** 2 * rng.uniform(0.5, 1.5, (ntiles, C))                          # tile variances
+    if count_one:
+        tv[:] = 0.0
+    s1 = (T * tm).astype(np.float32)
+    s2 = (T * (tv + tm ** 2)).astype(np.float32)
+    s1[:, 0] = 3.0 * T
+    s2[:, 0] = np.nextafter(np.float32(9.0 * T), np.float32(0))
+    part = np.stack([s1, s2], 1)
+    return {"partials": torch.from_numpy(part), "count": float(ntiles * T),
+            "gamma": torch.from_numpy(rng.uniform(-2, 2, C).astype(np.float32)), "beta": torch.from_numpy(rng.uniform(-1, 1, C).astype(np.float32)),
+            "rm": torch.from_numpy(rng.uniform(-1, 1, C).astype(np.float32)), "rv": torch.from_numpy(rng.uniform(0.5, 2, C).astype(np.float32))}
+
+
+def bn_finalize_reference(r, with_affine=True):
+    """numpy fp64 from the fp32 partials: the outputs of gs_bn_finalize and, per output, the sum of the magnitudes of its terms
+    (what one fp32 rounding of that output is relative to)"""
+    import numpy as np
+    p = r["partials"].numpy().astype(np.float64)
+    n, count = p.shape[0], r["count"]
+    C = p.shape[2]
+    gamma = r["gamma"].numpy().astype(np.float64) if with_affine else np.ones(C)
+    beta = r["beta"].numpy().astype(np.float64) if with_affine else np.zeros(C)
+    rm, rv = r["rm"].numpy().astype(np.float64), r["rv"].numpy().astype(np.float64)
+    eps, mom = float(np.float32(BN_EPS)), float(np.float32(BN_MOMENTUM))
+    S1, S2 = p[:, 0].sum(0), p[:, 1].sum(0)
+    mean = S1 / count
+    raw = S2 / count - mean * mean
+    var = np.maximum(raw, 0.0)
+    invstd = 1.0 / np.sqrt(var + eps)
+    scale = gamma * invstd
+    unb = var * (count / (count - 1.0)) if count > 1 else var
+    keep = float(np.float32(1.0) - np.float32(BN_MOMENTUM))
+    return {"mean": mean, "invstd": invstd, "scale": scale, "shift": beta - mean * scale, "rm": keep * rm + mom * mean, "rv": keep * rv + mom * unb,
+            "raw_var": raw,
+            "mag": {"mean": np.abs(mean), "invstd": invstd, "scale": np.abs(scale), "shift": np.abs(beta) + np.abs(mean * scale),
+                    "rm": np.abs(keep * rm) + np.abs(mom * mean), "rv": np.abs(keep * rv) + np.abs(mom * unb)}}
+
+
+def coeff_bound(ref, name, roundings):
+    """the largest |error| of output `name`: roundings[name] fp32 roundings, each at most 2^-24 of the magnitudes of its terms"""
+    return ref["mag"][name] * (roundings[name] * 2.0 ** -24)

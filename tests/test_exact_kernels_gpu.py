@@ -1,10 +1,16 @@
-"""Exact-integer kernel tests: the 16-bit convolution, data-gradient, weight-gradient and reduction kernels on integer
-operands against the fp64 references of tests/exact_reference.py, at ZERO tolerance.  Called through
+"""Exact-integer kernel tests: the 16-bit convolution, data-gradient, weight-gradient and reduction kernels and the
+BatchNorm / activation family (section G: forward apply, backward reduce / coefficients / apply, the head-source entry points) on
+integer operands against the fp64 references of tests/exact_reference.py, at ZERO tolerance.  Called through
 semantic_segmentation_amd.ops the way tests/test_gpu_kernels.py calls each kernel (channel-sliced inputs with poison outside
 the slice, output slices whose neighbours must stay untouched, NaN-filled outputs and workspaces where a kernel promises to
 overwrite), in fp16 and bf16.  Every comparison is assert_exact / torch.equal; the one allowance is the documented unit in
-the last place on NEGATIVE LeakyReLU(0.2) outputs (exact_reference.leaky_ok).  No case is skipped or filtered at run time.
-GPU only (`-m gpu`).
+the last place on NEGATIVE LeakyReLU(0.2) outputs (exact_reference.leaky_ok) of the convolution epilogues.  Section G draws its
+LeakyReLU operands as multiples of 5, where the slope product is exact, and has three allowances of its own, each stated where
+it is made: c1 / c2 = float32(s / count) may be the adjacent fp32 value where count is no power of two (_bn_chain); tanh outputs
+may be the 16-bit neighbour of the correctly rounded fp64 value, on at most TANH_NEIGHBOUR_SHARE of the elements
+(test_bn_act_tanh_per_element); gs_bn_finalize / gs_bn_eval_coeffs, which take 1 / sqrt, are bounded by their count of fp32
+roundings, 2^-24 each of the magnitude of the terms (test_bn_finalize_against_fp64, test_bn_eval_coeffs_against_fp64).
+No case is skipped or filtered at run time.  GPU only (`-m gpu`).
 Outputs and workspaces created through guarded() (out_buffer, nan32, zeros32) sit between guard words that are checked when the
 test ends; tensors allocated otherwise (weight packs, inputs) are not covered by that check."""
 import collections
@@ -935,3 +941,263 @@ def test_upconv8_image_wgrad_exact(case, dtn, dt):
     torch.cuda.synchronize()
     assert_exact(outs[0], expect32(r["dwm"]), f"upconv8_image_wgrad {_id(case)} {dtn} [class][tap][0][ci]")
     assert torch.equal(outs[0], outs[1])
+
+
+# ================================================================================================ G: BatchNorm / activation
+# gs_bn_act_apply, gs_bn_act_bwd_reduce -> gs_bn_bwd_coeffs -> gs_bn_act_bwd_apply and their head-source entry points on the
+# operands of exact_reference.bn_build: every fp32 intermediate is exactly representable (proven on the CPU in
+# tests/test_exact_reference_cpu.py), so z, zp, the tile sums, dgamma / dbeta and dy are compared at zero tolerance.
+def _act_code(name):
+    from semantic_segmentation_amd import _lib
+    return {"none": _lib.ACT_NONE, "relu": _lib.ACT_RELU, "leaky": _lib.ACT_LEAKY02}[name]
+
+
+def _vec(t):
+    return None if t is None else t.float().to(dev()).contiguous()
+
+
+def _bn_build_any(case):
+    return E.bn_head_build(case) if len(case) == 5 else E.bn_build(*case)
+
+
+def _bn_forward(ops, c, p, ref, dt, what):
+    """z into channels [8, 8 + C) of a C + 16 wide buffer (sentinel intact around it) and the pooled zp, exact"""
+    N, C, H, W = c["y"].shape
+    z = out_buffer((N, H, W, C), dt, C + 16, 8)
+    zp = out_buffer((N, H // 2, W // 2, C), dt) if c["pooled"] else None
+    ops.bn_act_apply(p["y"], p["scale"], p["shift"], _act_code(c["act"]), z, C + 16, 8, zp, p["keep"], c["keep_scale"])
+    torch.cuda.synchronize()
+    assert_slice(z, 8, channels_last(ref["z"]), what + " z")
+    if zp is not None:
+        assert_exact(zp, channels_last(ref["zp"]), what + " zp")
+
+
+def _bn_chain(ops, c, dt, what, forward=True, backward=True):
+    """one case through the forward apply and the backward chain.  The only comparison that is not an equality: c1 / c2 =
+    float32(s / count) may be the ADJACENT fp32 value where count is no power of two (the double quotient is rounded twice);
+    with a power-of-two count it is exact too."""
+    N, C, H, W = c["y"].shape
+    head = c["dza_kind"] == "head"
+    ref = E.bn_reference(c, dt)
+    p = {"y": sliced(channels_last(c["y"]), dt), "dzp": None if c["dzp"] is None else sliced(channels_last(c["dzp"]), dt),
+         "dzb": None if c["dzb"] is None else sliced(channels_last(c["dzb"]), dt),
+         "keep": None if c["keep"] is None else channels_last(c["keep"]).to(dev())}
+    p["sa"], p["ca"] = (2 * C, C) if c["dza_kind"] == "slice" else (C, 0)
+    p["dza"] = sliced(channels_last(c["dza"]), dt, p["sa"], p["ca"]) if c["dza_kind"] in ("slice", "dense") else None
+    for k in ("scale", "shift", "mean", "invstd", "c1", "c2"):
+        p[k] = _vec(c[k])
+    if forward and not head:
+        _bn_forward(ops, c, p, ref, dt, what)
+    if not backward:
+        return
+    act, act_b = _act_code(c["act"]), _act_code(c["act_b"])
+    if head:
+        dl, wh = c["dl"].to(dev()).contiguous(), c["w_head"].to(dev()).contiguous()
+    # ---- reduce: NaN-filled partials; the used tiles finite, their fp64 sum exact, nothing behind them written
+    used = ops.bn_bwd_tiles_used(N, H, W, c["pooled"])
+    part = nan32(ops.bn_partials_numel(ops.bn_bwd_tiles(N, H, W), C))
+    if head:
+        ops.bn_act_bwd_reduce_head(p["y"], dl, wh, p["scale"], p["shift"], p["mean"], p["invstd"], act, part)
+    else:
+        ops.bn_act_bwd_reduce(p["y"], p["dza"], p["sa"], p["ca"], p["dzp"], p["scale"], p["shift"], p["mean"], p["invstd"], act, part,
+                              p["dzb"], act_b, p["keep"], c["keep_scale"])
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(part[: used * 2 * C]).all()), what + f": a partial of the {used} used tiles was not written"
+    assert bool(torch.isnan(part[used * 2 * C:]).all()), what + f": written behind the {used} used tiles"
+    sums = torch.stack([ref["s1"], ref["s2"]])
+    assert_exact(stat_sums(part, used, C), sums, what + f" tile sums ({used} tiles)")
+    # ---- coefficients out of those partials (direct up to 512 tiles, two-stage above)
+    count = N * H * W
+    dgamma, dbeta, c1, c2 = nan32(C), nan32(C), nan32(C), nan32(C)
+    ops.bn_bwd_coeffs(part, used, C, count, 0.5, dgamma, dbeta, c1, c2)
+    torch.cuda.synchronize()
+    assert_exact(dbeta, expect32(ref["s1"], 0.5), what + " dbeta")
+    assert_exact(dgamma, expect32(ref["s2"], 0.5), what + " dgamma")
+    for got, s, name in ((c1, ref["s1"], "c1"), (c2, ref["s2"], "c2")):
+        want = torch.from_numpy((s.numpy() / float(count)).astype("float32")).to(dev())
+        ok = got == want
+        if not E.pow2(count):
+            ok = ok | (got == torch.nextafter(want, torch.full_like(want, float("inf")))) | (got == torch.nextafter(want, torch.full_like(want, -float("inf"))))
+        assert_exact(got, want, what + f" {name} ({used} tiles, count {count})", ok=ok)
+    # ---- apply with the dyadic c1 / c2 of the builder
+    dy = out_buffer((N, H, W, C), dt)
+    if head:
+        ops.bn_act_bwd_apply_head(p["y"], dl, wh, p["scale"], p["shift"], p["mean"], p["invstd"], p["c1"], p["c2"], act, dy)
+    else:
+        co = [p[k] if (c["bn"] or c["scale"] is not None) else None for k in ("mean", "invstd", "c1", "c2")]      # identity: all NULL
+        ops.bn_act_bwd_apply(p["y"], p["dza"], p["sa"], p["ca"], p["dzp"], p["scale"], p["shift"], co[0], co[1], co[2], co[3], act, c["bn"], dy,
+                             p["dzb"], act_b, p["keep"], c["keep_scale"])
+    torch.cuda.synchronize()
+    assert_exact(dy, expect16(channels_last(ref["dy"]), dt), what + " dy")
+
+
+@pytest.mark.parametrize("dtn,dt", DTS)
+@pytest.mark.parametrize("case", E.BN_CASES, ids=E.bn_id)
+def test_bn_act_chain_exact(case, dtn, dt):
+    """forward apply, backward reduce, coefficients and backward apply of one (shape, pooled, variant) at zero tolerance: see
+    exact_reference.BN_VARIANTS for the variants and BN_SHAPES for what each shape reaches"""
+    from semantic_segmentation_amd import ops
+    shape, pooled, _ = case
+    if shape in E.BN_TWO_STAGE_SHAPES:                         # what reaches the two-stage path of gs_bn_bwd_coeffs
+        assert ops.bn_bwd_tiles_used(*shape[:3], pooled) > 512
+    _bn_chain(ops, cached(_bn_build_any, case), dt, f"bn {E.bn_id(case)} {dtn}")
+
+
+@pytest.mark.parametrize("dtn,dt", DTS)
+@pytest.mark.parametrize("case", E.BN_FWD_ONLY_CASES, ids=E.bn_id)
+def test_bn_act_apply_grid_stride_exact(case, dtn, dt):
+    """1.18 M work items on the 4096-block grid: the grid-stride loop of the forward apply takes a second trip, tail first"""
+    from semantic_segmentation_amd import ops
+    N, H, W, C = case[0]
+    assert N * H * W * (C // 8) > 4096 * 256
+    _bn_chain(ops, cached(_bn_build_any, case), dt, f"bn forward {E.bn_id(case)} {dtn}", backward=False)
+
+
+@pytest.mark.parametrize("dtn,dt", DTS)
+@pytest.mark.parametrize("case", E.BN_HEAD_CASES, ids=_id)
+def test_bn_bwd_head_source_exact(case, dtn, dt):
+    """the head-source reduce and apply (dz_a formed in fp32 from dl and w_head, 1, 2 and 4 classes) at zero tolerance"""
+    from semantic_segmentation_amd import ops
+    _bn_chain(ops, cached(_bn_build_any, case), dt, f"bn head {_id(case)} {dtn}")
+
+
+def test_bn_bwd_head_source_two_lds_chunks_exact():
+    """2.17 M pixels in 1024 tiles of 2116: the logit gradients of a tile are staged in LDS in a chunk of 2048 and one of 68"""
+    from semantic_segmentation_amd import ops
+    N, H, W, C, ncls = E.BN_HEAD_TWO_CHUNKS
+    assert -(-N * H * W // ops.bn_bwd_tiles_used(N, H, W, False)) > 2048
+    _bn_chain(ops, cached(_bn_build_any, E.BN_HEAD_TWO_CHUNKS), torch.float16, f"bn head {_id(E.BN_HEAD_TWO_CHUNKS)} f16")
+
+
+def _check_neighbours(got, ref64_cl, what):
+    ok, share = E.neighbour16(got, ref64_cl)
+    print(f"{what}: {100 * share:.3f} % of the elements on the neighbour")
+    assert_exact(got, ref64_cl.to(got.dtype), what, ok=ok)
+    assert share <= E.TANH_NEIGHBOUR_SHARE, f"{what}: {share} of the elements sit on the neighbouring 16-bit value"
+
+
+@pytest.mark.parametrize("dtn,dt", DTS)
+@pytest.mark.parametrize("shape,pooled", E.TANH_CASES, ids=lambda v: _id(v) if isinstance(v, tuple) else ("pool" if v else "plain"))
+def test_bn_act_tanh_per_element(shape, pooled, dtn, dt):
+    """ACT_TANH (the generic kernel, NULL coefficients; the Pix2Pix output layer): the forward apply with and without the pool
+    and the bn = 0 backward apply, per element against fp64 -- the correctly rounded 16-bit value or its neighbour; no norm.
+    Why one place at most: the kernel forms tanhf(y) (a few fp32 ulp, relative error below 2^-21) and for the gradient
+    dz * (1 - t * t), whose cancellation multiplies the error of t by 2 t^2 / (1 - t^2) <= 9.1 for |y| <= 1.5 -- still below
+    2^-17 relative, while neighbouring 16-bit values are at least 2^-11 (fp16) or 2^-8 (bf16) apart, relatively.  The computed
+    value therefore lies within a small fraction of one 16-bit step of the true one, at most one rounding boundary lies
+    between them, and round-to-nearest lands on the same value or the adjacent one.  The share that does land on the neighbour
+    is about error / step: capped at TANH_NEIGHBOUR_SHARE, the figure the CPU test asserts for an fp32 evaluation of the same
+    operands.  zp must be EXACTLY the maximum over the z the kernel stored."""
+    from semantic_segmentation_amd import ops
+    from semantic_segmentation_amd._lib import ACT_TANH
+    N, H, W, C = shape
+    r = cached(E.tanh_build, shape, pooled)
+    what = f"tanh {_id(shape)} {dtn}"
+    y = sliced(channels_last(r["y"]), dt)
+    z = out_buffer((N, H, W, C), dt)
+    zp = out_buffer((N, H // 2, W // 2, C), dt) if pooled else None
+    ops.bn_act_apply(y, None, None, ACT_TANH, z, C, 0, zp)
+    dy = out_buffer((N, H, W, C), dt)
+    ops.bn_act_bwd_apply(y, sliced(channels_last(r["dz"]), dt), C, 0, None, None, None, None, None, None, None, ACT_TANH, False, dy)
+    torch.cuda.synchronize()
+    _check_neighbours(z, channels_last(r["z"]), what + " z")
+    if pooled:
+        assert torch.equal(zp, F.max_pool2d(z.permute(0, 3, 1, 2).float(), 2).permute(0, 2, 3, 1).to(dt)), what + " zp is not the max over the stored z"
+    _check_neighbours(dy, channels_last(r["dy"]), what + " dy")
+
+
+def _assert_coeffs(got, ref, roundings, what):
+    for name, t in got.items():
+        err = (t.double().cpu().numpy() - ref[name])
+        bound = E.coeff_bound(ref, name, roundings)
+        bad = ~(abs(err) <= bound)                             # a NaN is bad
+        assert not bad.any(), f"{what} {name}: channels {bad.nonzero()[0].tolist()[:8]} err {err[bad][:4]} bound {bound[bad][:4]}"
+
+
+@pytest.mark.parametrize("affine", [True, False], ids=["affine", "null"])
+@pytest.mark.parametrize("ntiles", E.BN_FINALIZE_TILES)
+@pytest.mark.parametrize("C", E.BN_FINALIZE_C)
+def test_bn_finalize_against_fp64(C, ntiles, affine):
+    """gs_bn_finalize on synthetic fp32 partials against numpy fp64, direct (<= 512 tiles) and two-stage; momentum 0.1.  Not
+    exact (1 / sqrt), so each output is bounded by its fp32 roundings, each at most 2^-24 of the magnitude of the terms it
+    touches (exact_reference.BN_FINALIZE_ROUNDINGS); the double sums before them (about 1e-9 of invstd at most, on the
+    channel with |mean| = 100 std) get no allowance of their own:
+      mean    1  (float) of the double mean
+      invstd  1  (float) of the double 1 / sqrt(var + eps)
+      scale   2  invstd, gamma * invstd
+      shift   5  on mean * scale: (float) mean, the two of scale, the product; on the result: the subtraction -- relative
+                 to |beta| + |mean * scale|
+      running 3  on each term of (1 - m) * r + m * x: the factor (1 - m, or (float) x), the product, the sum -- relative to
+                 |(1 - m) r| + |m x|
+    Channel 0 is constant with a raw variance below zero: it must clamp (invstd = 1 / sqrt(eps), not NaN); channel 1 has
+    |mean| = 100 std; with one tile, a second call has count = 1 (the unbiased variance must not divide by zero)."""
+    from semantic_segmentation_amd import ops
+    for count_one in ((False, True) if ntiles == 1 else (False,)):
+        r = E.bn_finalize_build(C, ntiles, count_one)
+        ref = E.bn_finalize_reference(r, affine)
+        part = nan32(ops.bn_partials_numel(ntiles, C))
+        part[: ntiles * 2 * C] = r["partials"].reshape(-1).to(dev())
+        out = {k: nan32(C) for k in ("scale", "shift", "mean", "invstd")}
+        rm, rv = zeros32(C), zeros32(C)
+        rm.copy_(r["rm"]), rv.copy_(r["rv"])
+        ops.bn_finalize(part, ntiles, C, r["count"], _vec(r["gamma"]) if affine else None, _vec(r["beta"]) if affine else None, rm, rv,
+                        E.BN_MOMENTUM, E.BN_EPS, out["scale"], out["shift"], out["mean"], out["invstd"])
+        torch.cuda.synchronize()
+        out.update(rm=rm, rv=rv)
+        what = f"bn_finalize C{C} tiles{ntiles} count{r['count']:.0f}"
+        _assert_coeffs(out, ref, E.BN_FINALIZE_ROUNDINGS, what)
+        import numpy as np
+        assert float(out["invstd"][0]) == float(np.float32(1.0 / np.sqrt(float(np.float32(E.BN_EPS))))), what + ": the constant channel did not clamp"
+
+
+@pytest.mark.parametrize("affine", [True, False], ids=["affine", "null"])
+@pytest.mark.parametrize("C", E.BN_FINALIZE_C)
+def test_bn_eval_coeffs_against_fp64(C, affine):
+    """gs_bn_eval_coeffs (all fp32) against numpy fp64 (exact_reference.BN_EVAL_ROUNDINGS): invstd 3 (the sum rv + eps counts
+    half, the square root, the division); scale 4 (+ the product); shift 6 (the four of scale and the product on rm * scale, the
+    subtraction) relative to |beta| + |rm * scale|; mean is rm itself."""
+    import numpy as np
+    from semantic_segmentation_amd import ops
+    r = E.bn_finalize_build(C, 2)
+    gamma = r["gamma"].numpy().astype(np.float64) if affine else np.ones(C)
+    beta = r["beta"].numpy().astype(np.float64) if affine else np.zeros(C)
+    rm, rv = r["rm"].numpy().astype(np.float64), r["rv"].numpy().astype(np.float64)
+    invstd = 1.0 / np.sqrt(rv + float(np.float32(E.BN_EPS)))
+    ref = {"mean": rm, "invstd": invstd, "scale": gamma * invstd, "shift": beta - rm * gamma * invstd,
+           "mag": {"mean": np.abs(rm), "invstd": invstd, "scale": np.abs(gamma * invstd), "shift": np.abs(beta) + np.abs(rm * gamma * invstd)}}
+    out = {k: nan32(C) for k in ("scale", "shift", "mean", "invstd")}
+    ops.bn_eval_coeffs(C, _vec(r["gamma"]) if affine else None, _vec(r["beta"]) if affine else None, _vec(r["rm"]), _vec(r["rv"]), E.BN_EPS,
+                       out["scale"], out["shift"], out["mean"], out["invstd"])
+    torch.cuda.synchronize()
+    _assert_coeffs(out, ref, E.BN_EVAL_ROUNDINGS, f"bn_eval_coeffs C{C}")
+
+
+def bn_rev_child():
+    """runs in a fresh process started with GSSEG_BN_REV=4: the cases of BN_REV_CASES, both dtypes, the same exact assertions"""
+    import os
+    from semantic_segmentation_amd import ops
+    assert os.environ.get("GSSEG_BN_REV") == "4"
+    for case in E.BN_REV_CASES:
+        for dtn, dt in DTS:
+            _bn_chain(ops, cached(_bn_build_any, case), dt, f"bn GSSEG_BN_REV=4 {E.bn_id(case)} {dtn}")
+    torch.cuda.synchronize()
+    for flat, n in _GUARDED:
+        assert bool((flat[:GUARD] == GUARD_VALUE).all()) and bool((flat[GUARD + n:] == GUARD_VALUE).all()), "guard words overwritten"
+    print("bn_rev_child OK")
+
+
+def test_bn_traversal_knob_reversed_backward_apply():
+    """GSSEG_BN_REV is read once per process and its default 3 never reverses the backward apply: three small cases here, then
+    the same in ONE fresh child process with GSSEG_BN_REV=4 (forward apply and reduce head first, backward apply tail first).
+    A failure here ends the test before the child is started."""
+    import os
+    import subprocess
+    import sys
+    from semantic_segmentation_amd import ops
+    for case in E.BN_REV_CASES:
+        _bn_chain(ops, cached(_bn_build_any, case), torch.float16, f"bn default traversal {E.bn_id(case)} f16")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, GSSEG_BN_REV="4")
+    res = subprocess.run([sys.executable, "-c", "from tests.test_exact_kernels_gpu import bn_rev_child; bn_rev_child()"], cwd=root, env=env,
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert res.returncode == 0 and "bn_rev_child OK" in res.stdout, res.stdout[-4000:]

@@ -300,3 +300,141 @@ def test_pix2pix_pack_cases_meet_the_conditions():
         expect32(E.image_fwd_build(case)["y"])
     for case in E.IMAGE_WGRAD_CASES:
         expect32(E.image_wgrad_build(case)["dwm"])
+
+
+# ------------------------------------------------------------------------------------------------ group G: BatchNorm / activation
+_BN_ALL = E.BN_CASES + E.BN_FWD_ONLY_CASES
+_HEADS = E.BN_HEAD_CASES + [E.BN_HEAD_TWO_CHUNKS]
+_BN_BUILT = {}
+
+
+def _bn(case):
+    """built once per process: the operands are the same for both dtypes, the order-independence test and the mutant test"""
+    if case not in _BN_BUILT:
+        _BN_BUILT[case] = E.bn_head_build(case) if len(case) == 5 else E.bn_build(*case)
+    return _BN_BUILT[case]
+
+
+def _bn_ident(case):
+    return "head-" + _id(case) if len(case) == 5 else E.bn_id(case)
+
+
+def test_bn_case_lists_hold_what_the_issue_lists():
+    plain = {s for s, p, v in E.BN_CASES if not p}
+    assert plain == set(E.BN_SHAPES) and len(E.BN_SHAPES) == 8
+    for s in E.BN_FULL_SHAPES:
+        assert {v for s2, p, v in E.BN_CASES if s2 == s and not p} == set(E.BN_VARIANTS) - {"pool_only"}
+    legal = {v for v, d in E.BN_VARIANTS.items() if d["dzb"] is None and not d["keep"]}
+    for s in E.BN_POOLED_SHAPES:
+        assert {v for s2, p, v in E.BN_CASES if s2 == s and p} == legal
+    acts = {(d["act"], d["dzb"]) for d in E.BN_VARIANTS.values()}
+    assert {("none", None), ("relu", None), ("leaky", None), ("relu", "none"), ("relu", "leaky")} <= acts
+    assert E.BN_POOLED_SHAPES == [(2, 9, 7, 64), (1, 65, 33, 128), (2, 64, 64, 64)] and E.BN_FWD_ONLY_CASES[0][0] == (2, 96, 96, 512)
+    assert E.BN_HEAD_CASES == [(2, 18, 22, 64, 2), (3, 45, 53, 64, 1), (2, 40, 40, 32, 4)] and E.BN_HEAD_TWO_CHUNKS == (1, 1472, 1472, 8, 3)
+    assert all(c in E.BN_CASES for c in E.BN_REV_CASES)
+
+
+def test_leaky_slope_is_exact_on_multiples_of_five_only():
+    """float32(x) * float32(0.2) == x / 5 for every multiple of 5 up to +-4000 (and of 5/4, the pre-activations under scales
+    down to 1/4); general integers are not exact, and require_fifths refuses them"""
+    x = torch.arange(-4000, 4001, 5, dtype=torch.float64)
+    E.require_fifths(x, x / 4, x * 4)
+    n = torch.arange(1, 4001, dtype=torch.float32)
+    exact = (n * torch.tensor(0.2)).double() * 5 == n.double()
+    assert bool(exact[4::5].all()) and 0.1 < float(exact.double().mean()) < 0.9
+    with pytest.raises(AssertionError):
+        E.require_fifths(torch.tensor([3.0]))
+
+
+@pytest.mark.parametrize("case", _BN_ALL + _HEADS, ids=_bn_ident)
+def test_bn_cases_are_exact_in_fp32_in_any_order(case):
+    """building a case asserts its conditions; then the backward evaluated in fp32, its sums over a shuffled pixel order in
+    runs of 64, equals the fp64 reference bit for bit, in both dtypes (the dtype enters through the rounded z of the pool).
+    Zeros of v, tied windows and negative gamma are present in every case that can hold them."""
+    c = _bn(case)
+    assert c["zero_share"] > 0 and c["gamma_negative"] > 0
+    if c["pooled"]:
+        assert c["tie_share"] > 0
+    for k in ("y", "dza", "dzb", "dzp"):
+        if c[k] is not None and c["dza_kind"] != "head":
+            for _, dt in DTS:
+                _representable(c[k], dt)
+    for i, (dtn, dt) in enumerate(DTS):
+        if case == E.BN_HEAD_TWO_CHUNKS and dtn != "f16":
+            continue                                            # runs in fp16 only
+        ref = E.bn_reference(c, dt)
+        got = E.bn_fp32_shuffled(c, dt, seed=i + 1)
+        for k in ("gh", "s1", "s2", "dy"):
+            assert torch.equal(got[k].double(), ref[k]), (k, dtn)
+        expect32(ref["s1"], 0.5), expect32(ref["s2"], 0.5), expect16(ref["dy"], dt)
+    if c["dza_kind"] == "head":                                 # the kernel's fp32 sum over the classes, in its order
+        dl, wh = c["dl"], c["w_head"]
+        t = dl[:, 0, None] * wh[0].view(1, -1, 1, 1)
+        for k in range(1, c["ncls"]):
+            t = t + dl[:, k, None] * wh[k].view(1, -1, 1, 1)
+        assert t.dtype == torch.float32 and torch.equal(t.double(), c["dza"])
+
+
+@pytest.mark.parametrize("case", E.BN_CASES + _HEADS, ids=_bn_ident)
+def test_comparer_separates_every_bn_mutant(case):
+    """each reference-level mutant that applies to a case changes dy (as the kernel stores it, rounded to the dtype) somewhere,
+    and assert_exact reports it; the sums move too, except where a mutant only moves a gradient inside its window"""
+    c = _bn(case)
+    for dtn, dt in DTS:
+        if case == E.BN_HEAD_TWO_CHUNKS and dtn != "f16":
+            continue                                            # runs in fp16 only
+        ref = E.bn_reference(c, dt)
+        want = expect16(channels_last(ref["dy"]), dt)
+        for m in E.BN_MUTANTS:
+            if not E.bn_mutant_applies(c, m):
+                continue
+            mut = E.bn_reference(c, dt, m)
+            got = expect16(channels_last(mut["dy"]), dt)
+            n = E.mismatches(got, want).shape[0]
+            assert n > 0, f"{_bn_ident(case)} {dtn}: mutant {m} is not told from the reference"
+            with pytest.raises(AssertionError, match="elements differ"):
+                E.assert_exact(got, want, m)
+            if m not in ("last", "unrounded"):
+                assert not (torch.equal(mut["s1"], ref["s1"]) and torch.equal(mut["s2"], ref["s2"])), (m, dtn)
+
+
+@pytest.mark.parametrize("shape,pooled", E.TANH_CASES, ids=lambda v: _id(v) if isinstance(v, tuple) else ("pool" if v else "plain"))
+def test_tanh_reference_in_fp32_rarely_lands_on_the_neighbour(shape, pooled):
+    """tanh and dz * (1 - tanh^2) evaluated in fp32 on the CPU and rounded to 16 bits: every element is the correctly rounded
+    fp64 value or its neighbour, and the neighbour's share stays under TANH_NEIGHBOUR_SHARE (the GPU test uses the same cap)"""
+    r = E.tanh_build(shape, pooled)
+    assert float(r["y"].abs().max()) == 1.5
+    for _, dt in DTS:
+        _representable(r["y"], dt)
+        t = torch.tanh(r["y"])
+        for got32, ref in ((t, r["z"]), (r["dz"] * (1 - t * t), r["dy"])):
+            ok, share = E.neighbour16(got32.to(dt), ref)
+            assert bool(ok.all()) and share <= E.TANH_NEIGHBOUR_SHARE, share
+        two_off = (E.ordered16(r["z"].to(dt)) + 2).to(torch.int16).view(dt)
+        assert not bool(E.neighbour16(two_off, r["z"])[0][r["z"] > 0].any())
+
+
+@pytest.mark.parametrize("ntiles", E.BN_FINALIZE_TILES)
+def test_bn_finalize_reference_and_its_bounds(ntiles):
+    """the edge channels are what they claim (a negative raw variance that clamps, |mean| = 100 std), and gs_bn_finalize's
+    arithmetic replayed in numpy fp32 meets the rounding-count bounds the GPU test asserts"""
+    import numpy as np
+    for C in E.BN_FINALIZE_C:
+        for count_one in ((False, True) if ntiles == 1 else (False,)):
+            r = E.bn_finalize_build(C, ntiles, count_one)
+            ref = E.bn_finalize_reference(r)
+            assert ref["raw_var"][0] < 0 and ref["invstd"][0] == 1.0 / np.sqrt(float(np.float32(E.BN_EPS)))
+            assert r["count"] == (1.0 if count_one else 64.0 * ntiles)
+            if not count_one:
+                assert 50 < abs(ref["mean"][1]) * ref["invstd"][1] < 200
+            f = np.float32
+            invstd = f(ref["invstd"])
+            sc = r["gamma"].numpy() * invstd
+            sh = r["beta"].numpy() - f(ref["mean"]) * sc
+            rm = (f(1) - f(E.BN_MOMENTUM)) * r["rm"].numpy() + f(E.BN_MOMENTUM) * f(ref["mean"])
+            var = np.maximum(ref["raw_var"], 0.0)
+            unb = var * (r["count"] / (r["count"] - 1.0)) if r["count"] > 1 else var
+            rv = (f(1) - f(E.BN_MOMENTUM)) * r["rv"].numpy() + f(E.BN_MOMENTUM) * f(unb)
+            assert sc.dtype == sh.dtype == rm.dtype == rv.dtype == np.float32
+            for name, got in (("mean", f(ref["mean"])), ("invstd", invstd), ("scale", sc), ("shift", sh), ("rm", rm), ("rv", rv)):
+                assert np.all(np.abs(got.astype(np.float64) - ref[name]) <= E.coeff_bound(ref, name, E.BN_FINALIZE_ROUNDINGS)), name
