@@ -22,46 +22,12 @@ import torch
 
 from .. import ops
 from .._lib import ACT_LEAKY02, ACT_NONE, ACT_RELU, ACT_TANH
-
-_TORCH_DT = {"f16": torch.float16, "bf16": torch.bfloat16}
-
-
-def _dtype_of(name):
-    import os
-    name = name or os.environ.get("GSSEG_DTYPE", "f16")
-    if name not in _TORCH_DT:
-        raise ValueError("compute dtype must be 'f16' or 'bf16'")
-    return name, _TORCH_DT[name]
+from ..engine_common import ParamIndex, _flush_nbt, bn_coeffs, compute_dtype, pack_key, pack_reuse_allowed
 
 
 def _need_cuda(x):
     if not x.is_cuda:
         raise RuntimeError("semantic_segmentation_amd Pix2Pix networks run on the MI355X only (no CPU / ATen fallback)")
-
-
-def _bn_coeffs(bn, partials, ntiles, C, count, training, dev, nbt_pending=None):
-    """scale/shift/mean/invstd [4,C] from conv-epilogue partial sums (train) or running statistics (eval).
-    nbt_pending: list collecting the `num_batches_tracked` counters of this pass -- the caller increments them with ONE
-    foreach launch (_flush_nbt) instead of a 5-us kernel per BatchNorm layer."""
-    coef = torch.empty((4, C), dtype=torch.float32, device=dev)
-    batch_stats = training or bn.running_mean is None
-    if batch_stats:
-        mom = bn.momentum
-        if training and bn.num_batches_tracked is not None:
-            if nbt_pending is not None and mom is not None:
-                nbt_pending.append(bn.num_batches_tracked)
-            else:
-                bn.num_batches_tracked.add_(1)
-        if mom is None:
-            mom = 1.0 / float(bn.num_batches_tracked.item())
-        upd = training and bn.running_mean is not None
-        ops.bn_finalize(partials, ntiles, C, count, bn.weight.detach(), bn.bias.detach(),
-                        bn.running_mean if upd else None, bn.running_var if upd else None, mom, bn.eps,
-                        coef[0], coef[1], coef[2], coef[3])
-    else:
-        ops.bn_eval_coeffs(C, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps,
-                           coef[0], coef[1], coef[2], coef[3])
-    return coef, batch_stats
 
 
 # GSSEG_PIX2PIX_DIRECT_IMAGE=0: run the outermost generator layer on the MFMA engine (4 class launches + tanh + layout pass)
@@ -84,35 +50,6 @@ def cached_geom(builder, *args, identity_slots=False, **kw):
             _GEOMS.clear()
         _GEOMS[key] = g
     return g
-
-
-class _ParamIndex:
-    """(name, owner module, leaf name) of every parameter in registration order -- the order autograd sees them.  Walking the module
-    tree costs ~0.1-0.2 ms per call and a step asked for it a dozen times; the tree of these networks is static while the
-    Parameter objects may be swapped (`.to()`), so the OWNERS are cached and the tensors are read from them on every call."""
-
-    def _pidx(self):
-        idx = self.__dict__.get("_pidx_cache")
-        if idx is None:
-            mods = dict(self.net.named_modules())
-            idx = []
-            for name, _ in self.net.named_parameters():
-                head, _, leaf = name.rpartition(".")
-                idx.append((name, mods[head], leaf))
-            self.__dict__["_pidx_cache"] = idx
-        return idx
-
-    def param_list(self):
-        return [m._parameters[leaf] for _, m, leaf in self._pidx()]
-
-    def param_names(self):
-        return [n for n, _, _ in self._pidx()]
-
-
-def _flush_nbt(pending):
-    if pending:
-        torch._foreach_add_(pending, 1)
-        pending.clear()
 
 
 class _PackCache:
@@ -159,15 +96,10 @@ class _PackCache:
         self._d.clear()              # (the captured tensors stay registered: graphs that read them may still be replayed)
 
 
-_NOCACHE = [0]
-
-
 def _ver(*ts):
-    from ..unet import unet_engine
-    if not unet_engine.PACK_CACHE:                   # GSSEG_PACK_CACHE=0 (loops that write parameters through `.data`)
-        _NOCACHE[0] += 1
-        return (_NOCACHE[0],)
-    return tuple((t.data_ptr(), t._version) for t in ts)
+    """version key of a pack made from the tensors ts: (data_ptr, _version) of each (engine_common.pack_key; GSSEG_PACK_CACHE=0,
+    for loops that write parameters through `.data`: a key that no earlier one equals)"""
+    return tuple(pack_key(t)[:2] for t in ts)
 
 
 class _EmitDict:
@@ -183,13 +115,13 @@ class _EmitDict:
 # =====================================================================================================
 # Generator
 # =====================================================================================================
-class GeneratorEngine(_ParamIndex):
+class GeneratorEngine(ParamIndex):
     def __init__(self, net, dtype=None):
         self.net = net
-        self.dtype, self.tdt = _dtype_of(dtype)
+        self.dtype, self.tdt = compute_dtype(dtype)
         self.packs = _PackCache()
         self._layer_of, self._merge_inputs = {}, {}      # per block depth: arch row / the three kernels of its merged pack
-        self.trust_versions = False      # see unet_engine.pack_reuse_allowed
+        self.trust_versions = False      # see engine_common.pack_reuse_allowed
         self.grad_ready_hook = self.after_backward = self.grad_fetch = None      # parallel.GradReducer.attach
 
     def blocks(self):
@@ -248,7 +180,6 @@ class GeneratorEngine(_ParamIndex):
         dev = x.device
         x = x.contiguous().float()
         arch = arch.to(dev)
-        from ..unet.unet_engine import pack_reuse_allowed
         if not pack_reuse_allowed(need_grad, self.trust_versions):
             self.packs.clear()       # training forwards always re-pack: `.data` writes (Betty) bump no version counter
 
@@ -287,7 +218,7 @@ class GeneratorEngine(_ParamIndex):
             ops.conv_igemm(g, L[k - 1], wf, y, None, part)
             coef, stats = (None, False)
             if has_bn:
-                coef, stats = _bn_coeffs(downnorm, part, mt, c[k], N * hs[k] * ws[k], training, dev, nbt_pending)
+                coef, stats = bn_coeffs(downnorm, part, mt, c[k], N * hs[k] * ws[k], training, dev, nbt_pending)
             sc, sh = (coef[0], coef[1]) if has_bn else (None, None)
             ctx["levels"][k] = dict(y=y, coef=coef, stats=stats, geom=g, wd=wd, inp=L[k - 1])
             if k < D:
@@ -328,7 +259,7 @@ class GeneratorEngine(_ParamIndex):
                 pslices = [part[cls * mt * 2 * cout_t:] for cls in range(4)] if part is not None else None
                 # the four sub-pixel classes in ONE launch (each is latency bound on its own at the script's batch size)
                 ops.conv_igemm_batch(geoms, R[d + 1], [pf[cls] for cls in range(4)], u, bias, pslices)
-                coef, stats = _bn_coeffs(upnorm, part, 4 * mt, cout_t, N * H2 * W2, training, dev, nbt_pending)
+                coef, stats = bn_coeffs(upnorm, part, 4 * mt, cout_t, N * H2 * W2, training, dev, nbt_pending)
                 keep, kscale = None, 1.0
                 if drop is not None and training and drop.p > 0:
                     if dropout_masks is not None:
@@ -449,12 +380,12 @@ class _GeneratorFunction(torch.autograd.Function):
 # =====================================================================================================
 # Discriminator
 # =====================================================================================================
-class DiscriminatorEngine(_ParamIndex):
+class DiscriminatorEngine(ParamIndex):
     def __init__(self, net, dtype=None):
         self.net = net
-        self.dtype, self.tdt = _dtype_of(dtype)
+        self.dtype, self.tdt = compute_dtype(dtype)
         self.packs = _PackCache()
-        self.trust_versions = False      # see unet_engine.pack_reuse_allowed
+        self.trust_versions = False      # see engine_common.pack_reuse_allowed
         self.grad_ready_hook = self.after_backward = self.grad_fetch = None      # parallel.GradReducer.attach
 
     def run(self, x):
@@ -478,7 +409,6 @@ class DiscriminatorEngine(_ParamIndex):
         x = x.contiguous().float()
         N, cin0, H, W = x.shape
         stages = self.layout()
-        from ..unet.unet_engine import pack_reuse_allowed
         if not pack_reuse_allowed(need_grad, self.trust_versions):
             self.packs.clear()       # training forwards always re-pack: `.data` writes (Betty) bump no version counter
         if cin0 > 4:
@@ -510,7 +440,7 @@ class DiscriminatorEngine(_ParamIndex):
             use_stats = training or bn.running_mean is None
             part = empty(ops.bn_partials_numel(mt, conv.out_channels), dtype=torch.float32) if use_stats else None
             ops.conv_igemm(g, cur, wf, y, None, part)
-            coef, stats = _bn_coeffs(bn, part, mt, conv.out_channels, N * oh * ow, training, dev, nbt_pending)
+            coef, stats = bn_coeffs(bn, part, mt, conv.out_channels, N * oh * ow, training, dev, nbt_pending)
             z = empty(N, oh, ow, conv.out_channels)
             ops.bn_act_apply(y, coef[0], coef[1], ACT_LEAKY02, z, conv.out_channels, 0)
             recs.append(dict(kind="mid", conv=conv, bn=bn, inp=cur, y=y, coef=coef, stats=stats, geom=g, wd=wd,

@@ -15,13 +15,11 @@ import torch
 
 from .. import ops
 from .._lib import ACT_NONE, ACT_RELU
-
-_TORCH_DT = {"f16": torch.float16, "bf16": torch.bfloat16}
+from ..engine_common import bn_coeffs, compute_dtype
 
 
 def _tdt():
-    import os
-    return _TORCH_DT[os.environ.get("GSSEG_DTYPE", "f16")]
+    return compute_dtype()[1]
 
 
 def _check(x, what):
@@ -68,20 +66,7 @@ class _Stage:
             self.wd = torch.empty((9, cin, cout), dtype=tdt, device=dev)
             ops.pack_weight(conv.weight.detach().contiguous(), wf, self.wd, False)
             ops.conv3x3(inp, wf, y, N, h, w, cin, cout, ops.TAPS3_FWD, None, part, in_stride=in_stride)
-        coef = torch.empty((4, cout), dtype=torch.float32, device=dev)
-        if batch_stats:
-            mom = bn.momentum
-            if training and bn.num_batches_tracked is not None:
-                bn.num_batches_tracked.add_(1)
-            if mom is None:
-                mom = 1.0 / float(bn.num_batches_tracked.item()) if bn.num_batches_tracked is not None else 0.0
-            upd = training and bn.running_mean is not None
-            ops.bn_finalize(part, ntiles, cout, N * h * w, bn.weight.detach(), bn.bias.detach(),
-                            bn.running_mean if upd else None, bn.running_var if upd else None, mom, bn.eps,
-                            coef[0], coef[1], coef[2], coef[3])
-        else:
-            ops.bn_eval_coeffs(cout, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps,
-                               coef[0], coef[1], coef[2], coef[3])
+        coef, _ = bn_coeffs(bn, part, ntiles, cout, N * h * w, training, dev)
         ops.bn_act_apply(y, coef[0], coef[1], ACT_RELU, z, z_stride, z_coff)
         self.inp, self.in_stride, self.image, self.y, self.coef, self.stats = inp, in_stride, image, y, coef, batch_stats
         self.N, self.h, self.w, self.cin, self.cout = N, h, w, cin, cout

@@ -27,8 +27,8 @@ import torch
 
 from .. import ops
 from .._lib import ACT_NONE, ACT_RELU
+from ..engine_common import ParamIndex, _flush_nbt, bn_coeffs, compute_dtype, pack_key, pack_reuse_allowed
 
-_TORCH_DT = {"f16": torch.float16, "bf16": torch.bfloat16}
 # eval-mode forward without a graph: fold BatchNorm into the conv weights (GSSEG_FOLD_BN=0 keeps the two-pass form)
 FOLD_BN_INFERENCE = os.environ.get("GSSEG_FOLD_BN", "1") != "0"
 # Weight gradients on a second HIP stream (opt-in, GSSEG_WGRAD_STREAM=1): +1.6 % on the bs=32 256^2 step (14.00 -> 13.78 ms),
@@ -58,28 +58,6 @@ class _UpRec:
     __slots__ = ("name", "zin", "cat", "geom_bwd", "geom_wg", "wd", "cin", "cout", "h", "w", "H2", "W2", "pt", "pl")
 
 
-# Reuse of the 16-bit weight packs between forwards (GSSEG_PACK_CACHE):
-#   "safe" (default, also "1"): a forward that keeps a graph (training: grad mode on and something requires grad) ALWAYS
-#       re-packs -- one launch, ~0.1 ms at 31 M parameters, inside bench.py's timed region anyway.  Betty's darts hypergradient
-#       perturbs the parameters through `p.data` (running_files/train_end2end_jsrt.py:287-292: Config(type="darts")), which
-#       no version counter sees; with this default the stock script gets the perturbed weights.  Packs are reused only by
-#       forwards without a graph (eval / torch.no_grad()), keyed on (data_ptr, _version): every torch in-place op, every
-#       optimiser (torch's and optim.py's fused ones) and load_state_dict bump the version.
-#   "versions": the version-keyed reuse for training forwards too (loops that never write through `.data`).
-#   "0": never reuse.
-_PC = os.environ.get("GSSEG_PACK_CACHE", "safe")
-PACK_CACHE = _PC != "0"
-PACK_CACHE_TRAINING = _PC == "versions"
-_NOCACHE = [0]
-
-
-def _pack_key(p: torch.Tensor):
-    if not PACK_CACHE:
-        _NOCACHE[0] += 1
-        return (_NOCACHE[0],)
-    return (p.data_ptr(), p._version, p.dtype, tuple(p.shape))
-
-
 STREAM_SMALL_CONV = os.environ.get("GSSEG_STREAM_CONV", "1") != "0"
 
 
@@ -96,12 +74,6 @@ def stream_conv(N, h, w, cin, cout):
     if N * tiles * (-(-cout // 64)) > 128:
         return False
     return ops.conv_igemm_mtiles(ops.geom_conv(N, h, w, cin, cout, 3, 1, 1)) == -(-M // 16)
-
-
-def pack_reuse_allowed(need_grad: bool, trust_versions: bool = False) -> bool:
-    """may a forward reuse the packs of an earlier one?  (see GSSEG_PACK_CACHE above; `trust_versions`: the engine's owner
-    vouches that parameters only change through version-bumping ops -- harness.py does, it owns the optimisers)"""
-    return PACK_CACHE and (PACK_CACHE_TRAINING or trust_versions or not need_grad)
 
 
 STEM_WKEY = "inc.double_conv.0.weight"                      # the image-end conv: told apart by name, its Cin may be a multiple of 8
@@ -168,26 +140,33 @@ def _segs(mode: str, cin: int, lo_len=None):
     return [(0, 0, cin), (0, 0, ll), (1, 0, cin)], 2 * cin + ll, cin + ll
 
 
-class UNetEngine:
+def _stage_keys(st: str):
+    """state-dict keys of plan stage `st`: (weight key, BatchNorm module key or None, transposed) -- "down2.3" ->
+    ("down2.maxpool_conv.1.double_conv.3.weight", "down2.maxpool_conv.1.double_conv.4", False), "up1.up" -> ("up1.up.weight", None, True)"""
+    if st.endswith(".up"):
+        return st + ".weight", None, True
+    blk, idx = st.rsplit(".", 1)
+    prefix = blk if (blk == "inc" or blk.endswith(".conv")) else blk + ".maxpool_conv.1"
+    return f"{prefix}.double_conv.{idx}.weight", f"{prefix}.double_conv.{int(idx) + 1}", False
+
+
+class UNetEngine(ParamIndex):
     """Executes UNet.forward / backward for a `UNet` module tree on the HIP kernels."""
 
     def __init__(self, net, dtype: str = "f16", precise: bool = False):
-        if dtype not in _TORCH_DT:
-            raise ValueError("dtype must be 'f16' or 'bf16'")
         self.net = net
-        self.dtype = dtype
+        self.dtype, self.tdt = compute_dtype(dtype)
         # precise forward (module docstring of forward_precise): activations / weights as hi+lo pairs of 16-bit values,
         # logits within ~1e-5 of the fp32 reference instead of ~4e-3; the backward pass is unchanged (it reads the hi halves)
-        self.plan = resolve_plan(precise, dtype, bool(getattr(net, "bilinear", False)))      # None: the default single 16-bit engine
+        self.plan = resolve_plan(precise, self.dtype, bool(getattr(net, "bilinear", False)))      # None: the default single 16-bit engine
         self.precise = self.plan is not None
         # "auto" (what UNet() builds): the mixed pair forward wherever it is implemented, the 16-bit engine elsewhere (an
         # explicit "mixed" / True raises there instead)
         self.auto = precise == "auto"
         self._warned_fallback = False    # "auto" names its fallback to the 16-bit engine once per engine
         self.dynamic_loss_scale = os.environ.get("GSSEG_DYNAMIC_LOSS_SCALE", "0") == "1"
-        self.tdt = _TORCH_DT[dtype]
         self._packs: Dict[str, tuple] = {}
-        self.trust_versions = False      # True: training forwards reuse version-keyed packs (see GSSEG_PACK_CACHE)
+        self.trust_versions = False      # True: training forwards reuse version-keyed packs (GSSEG_PACK_CACHE, engine_common.py)
         self._side_streams: Dict[torch.device, torch.cuda.Stream] = {}     # weight-gradient stream per device
         # data-parallel hooks (parallel.GradReducer): grads are allocated inside the reducer's flat buckets,
         # announced as soon as they are final (so the RCCL all-reduce overlaps the rest of backward), and
@@ -201,34 +180,7 @@ class UNetEngine:
         # and hands autograd nothing, instead of one 5-us AccumulateGrad add per parameter (~90); same sums, same order
         self.accumulate_grads = False
 
-    # ------------------------------------------------------------------ parameters
-    def _index(self):
-        """(owner module, leaf name) of every parameter and buffer, in registration order.  Walking the module tree costs
-        ~0.7 ms per call; the tree of a UNet is static, while the tensors themselves may be swapped (`.to()`, `.half()`)
-        -- so the owners are cached and the tensors are read from them on every call."""
-        idx = self.__dict__.get("_idx")
-        if idx is None:
-            mods = dict(self.net.named_modules())
-            def owners(named):
-                out = []
-                for name, _ in named:
-                    head, _, leaf = name.rpartition(".")
-                    out.append((name, mods[head], leaf))
-                return out
-            idx = (owners(self.net.named_parameters()), owners(self.net.named_buffers()), mods)
-            self.__dict__["_idx"] = idx
-        return idx
-
-    def param_items(self):
-        """(name, Parameter) in registration order -- the order autograd sees them."""
-        return [(n, m._parameters[leaf]) for n, m, leaf in self._index()[0]]
-
-    def buffer_dict(self):
-        return {n: m._buffers[leaf] for n, m, leaf in self._index()[1]}
-
-    def submodule(self, key: str):
-        return self._index()[2][key]
-
+    # ------------------------------------------------------------------ parameters (ParamIndex: param_items, buffer_dict, submodule)
     def _side_stream(self, dev):
         st = self._side_streams.get(dev)
         if st is None:
@@ -257,7 +209,7 @@ class UNetEngine:
                 if tuple(w.shape[2:]) != (3, 3) or name == STEM_WKEY:         # the image-end layer is not packed (any channel count)
                     continue
                 cout, cin = w.shape[0], w.shape[1]
-            key = _pack_key(w)
+            key = pack_key(w)
             ent = self._packs.get(name)
             want_f = conv_fwd or transposed
             if ent is not None and ent[0] == key and (ent[2] is not None or not need_dgrad) and (ent[1] is not None or not want_f):
@@ -277,7 +229,7 @@ class UNetEngine:
     def _packed(self, name: str, w: torch.Tensor, transposed: bool, need_dgrad: bool, need_fwd: bool = True):
         """16-bit K-major packs of a conv weight, cached until the Parameter is modified (need_fwd=False: a cached entry without
         its forward pack -- _prepack(conv_fwd=False) -- will do)."""
-        key = _pack_key(w)
+        key = pack_key(w)
         ent = self._packs.get(name)
         if ent is not None and ent[0] == key and (ent[2] is not None or not need_dgrad) and (ent[1] is not None or not need_fwd):
             return ent[1], ent[2]
@@ -295,7 +247,7 @@ class UNetEngine:
     def _packed_padded(self, name: str, w: torch.Tensor, cpad: int, need_dgrad: bool):
         """packs of a 3x3 conv weight whose input channels are zero-padded to cpad (an image of more than 4 channels enters
         the MFMA path as a 16-bit NHWC tensor with a multiple of 8 channels)"""
-        key = (_pack_key(w), cpad)
+        key = (pack_key(w), cpad)
         ent = self._packs.get(name + "|padded")
         if ent is not None and ent[0] == key and (ent[2] is not None or not need_dgrad):
             return ent[1], ent[2]
@@ -311,7 +263,7 @@ class UNetEngine:
     def _folded(self, wkey: str, bnkey: str, w, gamma, beta, rm, rv, eps: float, image: bool):
         """Inference: BatchNorm(eval) folded into the conv -- w' = w * gamma/sqrt(var+eps) per output channel and a bias
         beta - mean*gamma/sqrt(var+eps).  Cached until a Parameter or running statistic changes."""
-        key = tuple(_pack_key(t) for t in (w, gamma, beta, rm, rv)) + (eps,)
+        key = tuple(pack_key(t) for t in (w, gamma, beta, rm, rv)) + (eps,)
         ent = self._packs.get(wkey + "|folded")
         if ent is not None and ent[0] == key:
             return ent[1], ent[2]
@@ -377,31 +329,6 @@ class UNetEngine:
         recs: List[_ConvRec] = []
         ups: List[_UpRec] = []
 
-        def bn_coeffs(bnkey, ntiles, cout, count):
-            coef = empty(4, cout, dtype=torch.float32)       # scale, shift, mean, invstd
-            gamma, beta = params[bnkey + ".weight"], params[bnkey + ".bias"]
-            rm, rv = bufs.get(bnkey + ".running_mean"), bufs.get(bnkey + ".running_var")
-            batch_stats = training or rm is None
-            if batch_stats:
-                nbt = bufs.get(bnkey + ".num_batches_tracked")
-                bn_mod = self.submodule(bnkey)
-                mom = bn_mod.momentum
-                if training and nbt is not None:
-                    if mom is None:
-                        nbt.add_(1)                      # cumulative average: the factor needs the new count now
-                    else:
-                        nbt_pending.append(nbt)
-                if mom is None:
-                    mom = 1.0 / float(nbt.item()) if nbt is not None else 0.0
-                upd = training and rm is not None
-                ops.bn_finalize(partials, ntiles, cout, count, gamma.detach(), beta.detach(),
-                                rm if upd else None, rv if upd else None, mom, bn_mod.eps,
-                                coef[0], coef[1], coef[2], coef[3])
-            else:
-                ops.bn_eval_coeffs(cout, gamma.detach(), beta.detach(), rm, rv, self.submodule(bnkey).eps,
-                                   coef[0], coef[1], coef[2], coef[3])
-            return coef, batch_stats
-
         def conv_bn_relu(prefix, idx, inp, cin, cout, h, w, z, z_stride, z_coff, zp, image=False, wide=0):
             """prefix.double_conv.{idx} conv + .{idx+1} BN + ReLU.  wide = C0 > 4: `inp` is the image already converted to a
             16-bit NHWC tensor of cin = ceil8(C0) channels (zero padded); the weight's input channels are padded alike."""
@@ -452,7 +379,7 @@ class UNetEngine:
                     rec.tap_sums = empty(ntiles * 54, dtype=torch.float32) if batch_stats else torch.zeros(ntiles * 54, dtype=torch.float32, device=dev)
                 if batch_stats:
                     ops.stem_stats(inp, wst, partials, rec.tap_sums)
-                coef, rec.train_stats = bn_coeffs(bnkey, ntiles, cout, N * h * w)
+                coef, rec.train_stats = bn_coeffs(self.submodule(bnkey), partials, ntiles, cout, N * h * w, training, dev, nbt_pending)
                 ops.stem_fwd_bn(inp, wst, coef[0], coef[1], ACT_RELU, z)
                 rec.geom, rec.wd = None, None
                 rec.y, rec.coef, rec.z = None, coef, z
@@ -472,7 +399,7 @@ class UNetEngine:
                 else:
                     ops.conv_igemm(g, inp, wf, y, None, partials)
                 rec.geom, rec.wd = g, wd
-            coef, rec.train_stats = bn_coeffs(bnkey, ntiles, cout, N * h * w)
+            coef, rec.train_stats = bn_coeffs(self.submodule(bnkey), partials, ntiles, cout, N * h * w, training, dev, nbt_pending)
             if z is not None:
                 ops.bn_act_apply(y, coef[0], coef[1], ACT_RELU, z, z_stride, z_coff, zp)
             rec.y, rec.coef = y, coef               # (z is None: the caller applies BatchNorm + ReLU on its own load path)
@@ -579,8 +506,7 @@ class UNetEngine:
                 tmp = empty(N, g1 - g0, H, W, dtype=torch.float32)
                 ops.conv_smallcout_fwd(inp, wo[g0:g1].contiguous(), bo[g0:g1].contiguous(), tmp)
                 logits[:, g0:g1] = tmp
-        if nbt_pending:
-            torch._foreach_add_(nbt_pending, 1)
+        _flush_nbt(nbt_pending)
         ctx = None
         if need_grad:
             ctx = dict(recs=recs, ups=ups, x=x, z_last=inp, N=N, H=H, W=W, hs=hs, ws=ws_, C=C, training=training)
@@ -595,25 +521,17 @@ class UNetEngine:
         full = all(v == "xw" for v in self.plan.values())
         for st in STAGES:
             mode = eff[st]
-            if st.endswith(".up"):
-                wkey, transposed = st + ".weight", True
-            else:
-                blk, idx = st.rsplit(".", 1)
-                prefix = blk if (blk == "inc" or blk.endswith(".conv")) else blk + ".maxpool_conv.1"
-                wkey, transposed = f"{prefix}.double_conv.{idx}.weight", False
+            wkey, _, transposed = _stage_keys(st)
             w = params.get(wkey)
             if w is None or w.dim() != 4:
                 continue
             cin, cout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
             if st == "inc.0":                              # the image-end layer is not packed (any channel count)
                 continue
-            lo_len = None
-            if not full:
-                if transposed and mode == "1":
-                    continue                               # runs on the default LDS-DMA GEMM with the ordinary pack
-                if st.endswith(".conv.0") and eff[st[:-len(".conv.0")] + ".up"] == "1" and not self.net.bilinear:
-                    lo_len = cin // 2                      # the up half of the concat buffer carries no lo plane
-            key = (_pack_key(w), mode, lo_len)
+            if transposed and mode == "1" and not full:
+                continue                                   # runs on the default LDS-DMA GEMM with the ordinary pack
+            lo_len = self._lo_len(st, eff, cin)
+            key = (pack_key(w), mode, lo_len)
             ent = self._packs.get(wkey + "|segs")
             if ent is not None and ent[0] == key:
                 continue
@@ -641,11 +559,9 @@ class UNetEngine:
         statistic changes; every stale pack in ONE launch.  Returns False when a BatchNorm has no running statistics."""
         items, fresh = [], []
         for st in STAGES:
-            if st.endswith(".up"):
+            wkey, bnkey, transposed = _stage_keys(st)
+            if transposed:
                 continue
-            blk, idx = st.rsplit(".", 1)
-            prefix = blk if (blk == "inc" or blk.endswith(".conv")) else blk + ".maxpool_conv.1"
-            wkey, bnkey = f"{prefix}.double_conv.{idx}.weight", f"{prefix}.double_conv.{int(idx) + 1}"
             w = params.get(wkey)
             if w is None or w.dim() != 4 or st == "inc.0":
                 continue                                   # (the image-end stem folds nothing: it is one pass already)
@@ -654,12 +570,9 @@ class UNetEngine:
                 return False
             gamma, beta = params[bnkey + ".weight"], params[bnkey + ".bias"]
             cin, cout = w.shape[1], w.shape[0]
-            lo_len = None
-            if (not all(v == "xw" for v in self.plan.values()) and st.endswith(".conv.0") and eff[st[:-len(".conv.0")] + ".up"] == "1"
-                    and not self.net.bilinear):
-                lo_len = cin // 2
+            lo_len = self._lo_len(st, eff, cin)
             eps = self.submodule(bnkey).eps
-            key = tuple(_pack_key(t) for t in (w, gamma, beta, rm, rv)) + (eps, eff[st], lo_len)
+            key = tuple(pack_key(t) for t in (w, gamma, beta, rm, rv)) + (eps, eff[st], lo_len)
             ent = self._packs.get(wkey + "|fsegs")
             if ent is not None and ent[0] == key:
                 continue
@@ -680,14 +593,16 @@ class UNetEngine:
     def _seg_pack(self, wkey: str):
         return self._packs[wkey + "|segs"][1]
 
-    @staticmethod
-    def _wkey_of(st: str) -> str:
-        """state-dict key of the weight of plan stage `st` ("down2.3" -> "down2.maxpool_conv.1.double_conv.3.weight")"""
-        if st.endswith(".up"):
-            return st + ".weight"
-        blk, idx = st.rsplit(".", 1)
-        prefix = blk if (blk == "inc" or blk.endswith(".conv")) else blk + ".maxpool_conv.1"
-        return f"{prefix}.double_conv.{idx}.weight"
+    def _lo_len(self, st: str, eff: Dict[str, str], cin: int):
+        """leading channels of the lo plane of stage `st`'s input that are valid (None: all cin; the lo_len of _segs).  The decoder
+        entry conv behind a "1" transposed conv of a plan that is not all-"xw": that conv runs on the LDS-DMA GEMM and writes the
+        hi plane only, so the up half of the concat buffer carries no lo plane.  (Behind the bilinear up-sampling the lo plane is
+        written whenever the stage has an x_lo segment, and without one _segs does not look at lo_len.)  The segment packs and the
+        K / wrap the kernels are launched with both come from here."""
+        if (st.endswith(".conv.0") and eff[st[:-len(".conv.0")] + ".up"] == "1" and not self.net.bilinear
+                and not all(v == "xw" for v in self.plan.values())):
+            return cin // 2
+        return None
 
     def forward_precise(self, x: torch.Tensor, params: Dict[str, torch.Tensor], training: bool, need_grad: bool):
         """The pair forward: every activation and conv output travels as a PAIR of 16-bit values v = hi + lo (hi = 16-bit(v),
@@ -727,7 +642,7 @@ class UNetEngine:
         eff = dict(plan)
         for st_, m_ in plan.items():
             if m_ == "q":
-                w_ = params.get(self._wkey_of(st_))
+                w_ = params.get(_stage_keys(st_)[0])
                 lv = lvl_of[st_.split(".")[0]]
                 ok = (not st_.endswith(".up") and st_ != "inc.0" and w_ is not None and self.dtype == "f16"
                       and ops.conv3x3_q8_ok(ws_[lv], w_.shape[1], w_.shape[0]))
@@ -748,36 +663,12 @@ class UNetEngine:
         recs: List[_ConvRec] = []
         ups: List[_UpRec] = []
 
-        def bn_coef(bnkey, partials, ntiles, cout, count, batch_stats):
-            coef = empty(4, cout, dtype=torch.float32)
-            gamma, beta = params[bnkey + ".weight"], params[bnkey + ".bias"]
-            bn_mod = self.submodule(bnkey)
-            rm = bufs.get(bnkey + ".running_mean")
-            if batch_stats:
-                nbt = bufs.get(bnkey + ".num_batches_tracked")
-                mom = bn_mod.momentum
-                if training and nbt is not None:
-                    if mom is None:
-                        nbt.add_(1)
-                    else:
-                        nbt_pending.append(nbt)
-                if mom is None:
-                    mom = 1.0 / float(nbt.item()) if nbt is not None else 0.0
-                upd = training and rm is not None
-                ops.bn_finalize(partials, ntiles, cout, count, gamma.detach(), beta.detach(), rm if upd else None,
-                                bufs.get(bnkey + ".running_var") if upd else None, mom, bn_mod.eps,
-                                coef[0], coef[1], coef[2], coef[3])
-            else:
-                ops.bn_eval_coeffs(cout, gamma.detach(), beta.detach(), rm, bufs[bnkey + ".running_var"], bn_mod.eps,
-                                   coef[0], coef[1], coef[2], coef[3])
-            return coef
-
         def stage(prefix, idx, inp, cin, cout, h, w, zbuf, z_stride, want_lo, zp=None, zp_want_lo=False, image=False,
-                  lo_len=None, to_head=False):
+                  to_head=False):
             """prefix.double_conv.{idx} conv + BN + ReLU on pairs.  inp: fp32 image or a pair buffer [N,h,w,2*cin]; the z pair
             goes to channels [0,cout) / [z_stride/2, z_stride/2 + cout) of zbuf (pixel stride z_stride), the lo plane only when
             a consumer reads it; zp: pooled pair buffer [.., 2*cout].  to_head: BatchNorm + ReLU are left to the head's load
-            path (returns the record; nothing stored).  lo_len: leading channels of the input's lo plane that are valid."""
+            path (returns the record; nothing stored).  The valid part of the input's lo plane: self._lo_len, as the packs."""
             short = prefix.replace(".maxpool_conv.1", "") + f".{idx}"
             wkey, bnkey = f"{prefix}.double_conv.{idx}.weight", f"{prefix}.double_conv.{idx + 1}"
             wparam = params[wkey]
@@ -803,7 +694,7 @@ class UNetEngine:
                                     else torch.zeros(ntiles * 54, dtype=torch.float32, device=dev))
                 if batch_stats:
                     ops.stem_stats(inp, wst, partials, rec.tap_sums)
-                coef = bn_coef(bnkey, partials, ntiles, cout, N * h * w, batch_stats)
+                coef = bn_coeffs(self.submodule(bnkey), partials, ntiles, cout, N * h * w, training, dev, nbt_pending)[0]
                 if want_lo == 2:
                     ops.stem_fwd_bn_pair_q8(inp, wst, coef[0], coef[1], ACT_RELU, zbuf)
                 else:
@@ -814,7 +705,7 @@ class UNetEngine:
                 return rec
             if fold and not image and not batch_stats:
                 _, fpack, fbias = self._packs[wkey + "|fsegs"]
-                _, K, wrap = _segs(plan[short], cin, lo_len)
+                _, K, wrap = _segs(plan[short], cin, self._lo_len(short, plan, cin))
                 if to_head:                                # the head reads a dense pair
                     zd = empty(2, N, h, w, cout)
                     ops.conv3x3_segs(inp, fpack, zd[0], zd[1], N, h, w, K, wrap, cin, cout, in_stride=2 * cin, bias=fbias, act=ACT_RELU)
@@ -842,10 +733,10 @@ class UNetEngine:
                 qpack, wexp = self._seg_pack(wkey)
                 ops.conv3x3_q8(inp, qpack, wexp, y_hi, y_lo, N, h, w, cin, cout, in_stride=2 * cin, bn_partials=partials)
             else:
-                _, K, wrap = _segs(plan[short], cin, lo_len)
+                _, K, wrap = _segs(plan[short], cin, self._lo_len(short, plan, cin))
                 ops.conv3x3_segs(inp, self._seg_pack(wkey), y_hi, y_lo, N, h, w, K, wrap, cin, cout, in_stride=2 * cin,
                                  bn_partials=partials)
-            coef = bn_coef(bnkey, partials, ntiles, cout, N * h * w, batch_stats)
+            coef = bn_coeffs(self.submodule(bnkey), partials, ntiles, cout, N * h * w, training, dev, nbt_pending)[0]
             rec.y, rec.coef = y_hi, coef
             if wide_img:
                 rec.wd = self._packed_padded(wkey, wparam, rec.cin, True)[1] if need_grad else None
@@ -906,7 +797,6 @@ class UNetEngine:
             cat = cats[lvl]
             wkey = prefix + ".up.weight"
             up_mode = plan[prefix + ".up"]
-            up_lo_valid = True
             if bilinear:
                 # nn.Upsample(scale_factor=2, bilinear, align_corners=True) of the PAIR (unet_parts.py:49-50), straight into the up
                 # half of both planes of the concat buffer; the lo plane only when the consumer runs an x_lo segment
@@ -916,13 +806,11 @@ class UNetEngine:
                 ops.upsample2x_bilinear_fwd_pair(inp, inp[..., cin_t:], cat, cat[..., 2 * cout_t:] if want else None, N, h, w,
                                                  cin_t, H2, W2, in_stride=2 * cin_t, out_stride=4 * cout_t, out_coff=cout_t,
                                                  ooy=pt, oox=pl)
-                up_lo_valid = want
             elif up_mode == "1" and not full:
                 # x_hi . w_hi on the LDS-DMA pointwise GEMM, hi plane only: the consumer's x_lo segment skips the up half
                 wf, _ = self._packed(wkey, params[wkey], True, need_grad)
                 ops.upconv2x2_fwd(inp, wf, params[prefix + ".up.bias"].detach(), cat, N, 1, h, w, cin_t, cout_t, 1, H2, W2,
                                   in_stride=2 * cin_t, out_stride=4 * cout_t, out_coff=cout_t, ooy=pt, oox=pl)
-                up_lo_valid = False
                 if reads_lo(prefix + ".conv.0") == 2:
                     # the consumer is a "q" stage: the q chunks of the up half -- hi8 from the hi plane just written, lo8 = 0 (its
                     # x_lo . w_hi term then covers the skip channels only, exactly like the 16-bit "lo_len" segment)
@@ -952,8 +840,7 @@ class UNetEngine:
             cmid = params[prefix + ".conv.double_conv.0.weight"].shape[0]     # in_channels // 2 when bilinear
             cout3 = params[prefix + ".conv.double_conv.3.weight"].shape[0]
             zmid = empty(N, H2, W2, 2 * cmid)
-            stage(prefix + ".conv", 0, cat, 2 * cout_t, cmid, H2, W2, zmid, 2 * cmid, reads_lo(prefix + ".conv.3"),
-                  lo_len=None if up_lo_valid else cout_t)
+            stage(prefix + ".conv", 0, cat, 2 * cout_t, cmid, H2, W2, zmid, 2 * cmid, reads_lo(prefix + ".conv.3"))
             if j < 4:
                 zout = empty(N, H2, W2, 2 * cout3)
                 nxt_lo = True if bilinear else reads_lo(f"up{j + 1}.up")      # (the pair up-sampling interpolates both planes)
@@ -983,8 +870,7 @@ class UNetEngine:
         else:
             ops.head1x1_fwd_split(zl_hi, zl_lo, params["outc.conv.weight"].detach().contiguous(),
                                   params["outc.conv.bias"].detach(), logits)
-        if nbt_pending:
-            torch._foreach_add_(nbt_pending, 1)
+        _flush_nbt(nbt_pending)
         ctx = None
         if need_grad:
             ctx = dict(recs=recs, ups=ups, x=x, z_last=z_last, N=N, H=H, W=W, hs=hs, ws=ws_, C=C, training=training)

@@ -31,8 +31,7 @@ class UNet(nn.Module):
         self.up4 = (Up(128, 64, bilinear))
         self.outc = (OutConv(64, n_classes))
         # 16-bit storage/MFMA dtype of the engine: fp16 (default: 8x finer mantissa than bf16 at the same
-        # MFMA rate; gradients are loss-scaled internally) or bf16.  Not part of the state dict.
-        dt = compute_dtype or os.environ.get("GSSEG_DTYPE", "f16")
+        # MFMA rate; gradients are loss-scaled internally) or bf16 (compute_dtype, else GSSEG_DTYPE).  Not part of the state dict.
         # Numerics mode of the forward.  The reference's forward is plain fp32 (unet/unet_model.py:26-37) and the
         # north star asks for logits within 1e-3 of it, so the DEFAULT is the mode that meets that bound:
         #   precise=None / "auto" (GSSEG_PRECISE unset or "auto"): the "mixed" pair forward -- every tensor a hi/lo pair of 16-bit
@@ -45,7 +44,7 @@ class UNet(nn.Module):
         if precise is None:
             env = os.environ.get("GSSEG_PRECISE", "auto")
             precise = {"0": False, "1": True, "": "auto"}.get(env, env)
-        object.__setattr__(self, "_engine", UNetEngine(self, dt, precise=precise))
+        object.__setattr__(self, "_engine", UNetEngine(self, compute_dtype, precise=precise))
         # fp16 backward: gradients are carried times a static power-of-two scale that assumes a mean-reduced loss;
         # dynamic_loss_scale=True renormalises the incoming gradient on the device (sum-reduced losses, GradScaler, ...)
         if dynamic_loss_scale is not None:

@@ -62,14 +62,13 @@ class UNet3D(nn.Module):
         self.s_block2 = UpConv3DBlock(in_channels=l3, res_channels=l2)
         self.s_block1 = UpConv3DBlock(in_channels=l2, res_channels=l1, num_classes=num_classes, last_layer=True)
         self.in_channels, self.num_classes = in_channels, num_classes
-        dt = compute_dtype or os.environ.get("GSSEG_DTYPE", "f16")
         # numerics mode, as unet.UNet: the reference's forward is plain fp32 (unet3d.py:89-126), the north star asks for logits within
         # 1e-3, so the default (precise=None / "auto", GSSEG_PRECISE unset) is the "mixed" pair forward (unet3d_engine.forward_pair);
         # precise=False (GSSEG_PRECISE=0) = single 16-bit storage (~2.4e-3), precise=True = correction segments on every conv.
         if precise is None:
             env = os.environ.get("GSSEG_PRECISE", "auto")
             precise = {"0": False, "1": True, "": "auto"}.get(env, env)
-        object.__setattr__(self, "_engine", UNet3DEngine(self, dt, precise=precise))
+        object.__setattr__(self, "_engine", UNet3DEngine(self, compute_dtype, precise=precise))
 
     @property
     def engine(self):

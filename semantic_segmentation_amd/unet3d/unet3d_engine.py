@@ -19,8 +19,8 @@ import torch.nn.functional as F
 
 from .. import ops
 from .._lib import ACT_RELU
+from ..engine_common import ParamIndex, bn_coeffs, compute_dtype
 
-_TORCH_DT = {"f16": torch.float16, "bf16": torch.bfloat16}
 K3 = [(kd, ky, kx) for kd in range(3) for ky in range(3) for kx in range(3)]
 
 
@@ -119,15 +119,14 @@ class _Stage:
                  "D", "H", "W", "first", "x3", "halo", "wide")
 
 
-class UNet3DEngine:
+class UNet3DEngine(ParamIndex):
     def __init__(self, net, dtype="f16", precise=None):
-        if dtype not in _TORCH_DT:
-            raise ValueError("dtype must be 'f16' or 'bf16'")
-        self.net, self.dtype, self.tdt = net, dtype, _TORCH_DT[dtype]
+        self.net = net
+        self.dtype, self.tdt = compute_dtype(dtype)
         # numerics mode (as UNetEngine): None = single 16-bit storage (logits ~2.4e-3 from the fp32 reference); a plan = the pair
         # forward (forward_pair): every tensor a hi/lo pair, correction MFMA segments where the plan says so.  "auto" falls back
         # to the 16-bit engine for configurations the pair forward does not cover.
-        self.plan = resolve_plan3d(precise, dtype)
+        self.plan = resolve_plan3d(precise, self.dtype)
         self.auto = precise == "auto"
         self._warned_fallback = False    # "auto" names its fallback to the 16-bit engine once per engine
         # data-parallel hooks (parallel.GradReducer.attach): gradients announced as they become final, the compute stream
@@ -178,25 +177,6 @@ class UNet3DEngine:
 
         stages: List[_Stage] = []
 
-        def bn_coeffs(bn, bias, part, ntiles, C, count):
-            coef = empty(4, C, dtype=torch.float32)
-            batch = training or bn.running_mean is None
-            if batch:
-                if training and bn.num_batches_tracked is not None:
-                    bn.num_batches_tracked.add_(1)
-                mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked.item())
-                upd = training and bn.running_mean is not None
-                ops.bn_finalize(part, ntiles, C, count, bn.weight.detach(), bn.bias.detach(),
-                                bn.running_mean if upd else None, bn.running_var if upd else None, mom, bn.eps,
-                                coef[0], coef[1], coef[2], coef[3])
-                if upd and bias is not None:       # statistics were taken before the bias: mean(y + b) = mean(y) + b
-                    bn.running_mean.add_(bias.detach(), alpha=mom)
-            else:
-                rm = bn.running_mean if bias is None else (bn.running_mean - bias.detach())
-                ops.bn_eval_coeffs(C, bn.weight.detach(), bn.bias.detach(), rm.contiguous(), bn.running_var, bn.eps,
-                                   coef[0], coef[1], coef[2], coef[3])
-            return coef, batch
-
         def conv_bn_relu(conv, bn, inp, in_stride, in_coff, cin, D, H, W, z, z_stride, z_coff, first=False):
             cout = conv.out_channels
             st = _Stage()
@@ -236,7 +216,7 @@ class UNet3DEngine:
                     part = empty(ops.bn_partials_numel(nt, cout), dtype=torch.float32) if batch else None
                     ops.conv_igemm(g, inp, wf, y, None, part)
                 st.geom, st.wd = g, wd
-            st.coef, st.stats = bn_coeffs(bn, conv.bias, part, nt, cout, NB * D * H * W)
+            st.coef, st.stats = bn_coeffs(bn, part, nt, cout, NB * D * H * W, training, dev, conv_bias=conv.bias)
             ops.bn_act_apply(y, st.coef[0], st.coef[1], ACT_RELU, z, z_stride, z_coff)
             st.y = y
             if need_grad:
@@ -344,7 +324,7 @@ class UNet3DEngine:
         level = {"a_block1": 0, "a_block2": 1, "a_block3": 2, "bottleNeck": 3, "s_block3": 2, "s_block2": 1, "s_block1": 0}
         for st_, m_ in self.plan.items():
             if m_ == "q":
-                conv = net.get_submodule(st_)
+                conv = self.submodule(st_)
                 ok = (not st_.endswith("upconv1") and self.dtype == "f16"
                       and ops.conv3x3_q8_ok(W0 >> level[st_.split(".")[0]], conv.in_channels, conv.out_channels))
                 if not ok:
@@ -392,7 +372,7 @@ class UNet3DEngine:
             return 2 if plan[st_name] == "q" else 1
         dev = x.device
         x = x.contiguous().float()
-        names = {id(m): n for n, m in net.named_modules()}
+        names = {id(self.submodule(n)): n for n in lay}       # conv module -> its stage name
 
         def empty(*shape, dtype=tdt):
             return torch.empty(shape, dtype=dtype, device=dev)
@@ -400,7 +380,7 @@ class UNet3DEngine:
         # every stale segment pack in ONE launch
         items, qitems, packs = [], [], {}
         for st_name, (segs, K, _) in lay.items():
-            conv = net.get_submodule(st_name)
+            conv = self.submodule(st_name)
             cout, cin = conv.out_channels, conv.in_channels
             pack = empty(27, cout, K)
             if segs == "q":
@@ -418,32 +398,13 @@ class UNet3DEngine:
         if need_grad:                              # the backward's data-gradient packs (16-bit, as the default engine): one launch
             ditems = []
             for st_name in lay:
-                conv = net.get_submodule(st_name)
+                conv = self.submodule(st_name)
                 cout, cin = conv.out_channels, conv.in_channels
                 dpacks[st_name] = empty(27, cin, cout)
                 ditems.append((conv.weight.detach().reshape(cout, cin, 27, 1), None, dpacks[st_name], False))
             ops.pack_weight_multi(ditems)
 
         stages: List[_Stage] = []
-
-        def bn_coeffs(bn, bias, part, ntiles, C, count):
-            coef = empty(4, C, dtype=torch.float32)
-            batch = training or bn.running_mean is None
-            if batch:
-                if training and bn.num_batches_tracked is not None:
-                    bn.num_batches_tracked.add_(1)
-                mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked.item())
-                upd = training and bn.running_mean is not None
-                ops.bn_finalize(part, ntiles, C, count, bn.weight.detach(), bn.bias.detach(),
-                                bn.running_mean if upd else None, bn.running_var if upd else None, mom, bn.eps,
-                                coef[0], coef[1], coef[2], coef[3])
-                if upd and bias is not None:       # statistics were taken before the bias: mean(y + b) = mean(y) + b
-                    bn.running_mean.add_(bias.detach(), alpha=mom)
-            else:
-                rm = bn.running_mean if bias is None else (bn.running_mean - bias.detach())
-                ops.bn_eval_coeffs(C, bn.weight.detach(), bn.bias.detach(), rm.contiguous(), bn.running_var, bn.eps,
-                                   coef[0], coef[1], coef[2], coef[3])
-            return coef, batch
 
         def stage(conv, bn, inp, in_stride, cin, D, H, W, z_hi, z_lo, z_stride, z_coff, first=False, z_q8=False, zp=None):
             """conv (+ bias folded into BatchNorm) -> BN -> ReLU on pairs; the z pair goes to z_hi / z_lo (views; both take
@@ -494,7 +455,7 @@ class UNet3DEngine:
                     ops.conv3d3_segs(inp, packs[names[id(conv)]], y_hi, y_lo, NB, D, H, W, K, wrap, cin, cout, in_stride, 0, part, wrap_to=wto)
                 st.halo = True
                 st.wd = dpacks.get(names[id(conv)])
-            st.coef, st.stats = bn_coeffs(bn, conv.bias, part, nt, cout, NB * D * H * W)
+            st.coef, st.stats = bn_coeffs(bn, part, nt, cout, NB * D * H * W, training, dev, conv_bias=conv.bias)
             if z_q8:
                 ops.bn_act_apply_split_q8(y_hi, y_lo, st.coef[0], st.coef[1], ACT_RELU, z_hi, z_lo, True, z_stride, z_coff)
             elif zp is not None:
@@ -612,7 +573,7 @@ class UNet3DEngine:
         D0, H0, W0 = dims[0]
         S = float(2 ** round(math.log2(NB * D0 * H0 * W0)))
         inv_s = 1.0 / S
-        names = {id(p): n for n, p in net.named_parameters()}
+        names = {id(p): n for n, p in self.param_items()}
         # a gradient is announced to the reducer (bucketed all-reduce overlapped with the rest of backward) once ALL its
         # contributions are in: the decoder blocks' shared BatchNorm3d is used by two stages
         from ..parallel import GradEmitter
@@ -755,7 +716,7 @@ class _UNet3DFunction(torch.autograd.Function):
         if ctx.ectx is None:
             raise RuntimeError("UNet3D forward ran without gradient tracking")
         grads = ctx.engine.backward(ctx.ectx, dlogits)
-        names = [n for n, _ in ctx.engine.net.named_parameters()]
+        names = ctx.engine.param_names()
         fetch = ctx.engine.grad_fetch               # data parallel: the reduced gradients (parallel.GradReducer.fetch)
         out = [(fetch(n) if (fetch is not None and n in grads) else grads.get(n)) if p.requires_grad else None
                for n, p in zip(names, ctx.plist)]
@@ -763,6 +724,6 @@ class _UNet3DFunction(torch.autograd.Function):
 
 
 def run_unet3d(engine, x):
-    plist = tuple(p for p in engine.net.parameters())
+    plist = tuple(engine.param_list())
     need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in plist)
     return _UNet3DFunction.apply(engine, engine.net.training, need_grad, x, *plist)
