@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GS_ABI_VERSION 52
+#define GS_ABI_VERSION 53
 
 enum GsDtype { GS_F16 = 0, GS_BF16 = 1 };
 enum GsStatus { GS_OK = 0, GS_EINVAL = -1, GS_ELAUNCH = -2, GS_EUNSUPPORTED = -3 };
@@ -271,6 +271,14 @@ int gs_bn_act_bwd_apply(const void* y, const void* dz_a, int sa, int coff_a, con
                         const float* scale, const float* shift, const float* mean, const float* invstd,
                         const float* c1, const float* c2, int act, int bn, void* dy, int N, int H, int W, int C,
                         int dtype, void* stream);
+/* Kernel form of the PLAIN reduce / apply launches (dz_a only, identity or ReLU, no pool, no head source): 0 = normal
+ * (the default), 1 = slim: at most 96 VGPRs, so its waves fit on a SIMD beside the two waves of a weight-gradient block
+ * running on another stream.  Bit-identical output; slower when nothing runs beside it.  Process-wide, like
+ * gs_conv3x3_set_kernel_form(): set it around the launches it is meant for.  Every other launch ignores it. */
+int gs_bn_bwd_set_form(int form);
+/* Traversal direction of the element-wise passes, a bit mask: 1 forward apply, 2 backward reduce, 4 backward apply walk the
+ * tensor tail first (results do not depend on it).  -1 = the GSSEG_BN_REV environment value (default 3).  Process-wide. */
+int gs_bn_set_traversal(int mask);
 
 /* MaxPool3d(2, stride 2) on NDHWC 16-bit volumes (GenSeg-3D/UNet3D/unet3d.py:37,44).  fwd: z [NB,D,H,W,*] (strided) ->
  * zp [NB,D/2,H/2,W/2,C].  bwd: dz (dense, OVERWRITE) = dres[pix*stride + coff + c] (skip gradient, may be NULL)
@@ -626,6 +634,9 @@ int gs_upconv2x2_wgrad_slabs(const void* x, const void* dy, float* ws, int N, in
  * atomics of gs_conv3x3_wgrad and the gs_unpack_wgrad pass (autograd of unet_parts.py:16,19). */
 int64_t gs_conv3x3_wgrad_ws_floats(int N, int H, int W, int Cin, int Cout);
 int gs_conv3x3_wgrad_parts(int N, int H, int W, int Cin, int Cout);
+/* which kernel gs_conv3x3_wgrad / _slabs launch for this shape: 0 = the register-staged kernel (W < 24), 1 = the LDS-DMA
+ * kernel, 2 = its 128-cout form.  Forms 0 and 2 leave 96 VGPRs per SIMD lane to a kernel running beside them. */
+int gs_conv3x3_wgrad_family(int W, int Cout);
 int gs_conv3x3_wgrad_slabs(const void* x, const void* dy, float* ws, int N, int H, int W, int Cin, int in_pix_stride,
                            int in_coff, int Cout, int out_pix_stride, int out_coff, int dtype, void* stream);
 int gs_wgrad_reduce_unpack(const float* ws, int nparts, float* grad, int A, int B, int taps, int transposed,

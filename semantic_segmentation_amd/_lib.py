@@ -18,7 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 GS_F16, GS_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LEAKY02, ACT_TANH = 0, 1, 2, 3
 GS_MAX_TAPS = 64
-ABI_VERSION = 52
+ABI_VERSION = 53
 
 
 class GsConvGeom(ctypes.Structure):
@@ -82,6 +82,7 @@ PROTOTYPES = {
     "gs_conv3x3_wgrad": (c_int, [_P, _P, _F] + [c_int] * 10 + [c_void_p]),
     "gs_conv3x3_wgrad_ws_floats": (c_int64, [c_int] * 5),
     "gs_conv3x3_wgrad_parts": (c_int, [c_int] * 5),
+    "gs_conv3x3_wgrad_family": (c_int, [c_int] * 2),
     "gs_conv3x3_wgrad_slabs": (c_int, [_P, _P, _F] + [c_int] * 10 + [c_void_p]),
     "gs_wgrad_reduce_unpack": (c_int, [_F, c_int, _F, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "gs_conv_wgrad": (c_int, [POINTER(GsConvGeom), _P, _P, _F, c_int, c_void_p]),
@@ -106,6 +107,8 @@ PROTOTYPES = {
     "gs_bn_bwd_tiles_used": (c_int, [c_int, c_int, c_int, c_int]),
     "gs_bn_act_bwd_reduce": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, _P, c_float, _F, _F, _F, _F, c_int, _F]
                              + [c_int] * 5 + [c_void_p]),
+    "gs_bn_bwd_set_form": (c_int, [c_int]),
+    "gs_bn_set_traversal": (c_int, [c_int]),
     "gs_bn_bwd_coeffs": (c_int, [_F, c_int, c_int, c_double, c_float, _F, _F, _F, _F, c_void_p]),
     "gs_bn_act_bwd_apply": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, _P, c_float, _F, _F, _F, _F, _F, _F, c_int,
                                     c_int, _P]

@@ -114,9 +114,16 @@ __global__ __launch_bounds__(256) void bn_bwd_coeffs_kernel(const T* __restrict_
 // Traversal direction of the three element-wise passes (GSSEG_BN_REV bit mask: 1 forward apply, 2 backward reduce, 4 backward
 // apply run tail first).  Each pass streams a tensor that the previous kernel has just written (or read) head to tail: its
 // tail is what the 256 MB Infinity Cache still holds, so a pass that starts there takes part of its reads from the cache.
+// gs_bn_set_traversal() overrides the mask for the process (tests compare both directions; -1 = back to the environment's).
+static int g_traversal = -1;
 static int bn_traversal() {
     static const int v = getenv("GSSEG_BN_REV") ? atoi(getenv("GSSEG_BN_REV")) : 3;     // measured: 14.62 -> 14.53 ms per step
-    return v;
+    return g_traversal >= 0 ? g_traversal : v;
+}
+extern "C" int gs_bn_set_traversal(int mask) {
+    GS_CHECK_ARG(mask >= -1 && mask <= 7, "gs_bn_set_traversal: mask must be -1 (GSSEG_BN_REV / default) or 0..7");
+    g_traversal = mask;
+    return GS_OK;
 }
 
 // ---- forward apply -------------------------------------------------------------------------------
@@ -246,10 +253,15 @@ struct BwdArgs {
 // registers are compiled out (145-164 VGPRs otherwise: three waves per SIMD)
 // RN: a LeakyReLU is involved, the one slope whose product rounds: g * act'(v) goes through mul_rn.  g * 0 and g * 1 are exact
 // however they are fused, so the identity / ReLU launches (every launch of the U-Nets) take RN = false and pay nothing for it.
-template <int DT, bool POOL, bool APPLY, bool GENERIC, int HEAD = 0, bool EXTRA = true, bool RN = false>   // HEAD: 0 = tensor sources; 2 / 4 = a head of <= 2 / 4 outputs
-__global__ __launch_bounds__(256) void bn_act_bwd_kernel(const BwdArgs a) {
+// SLIM: the plain U-Net form (one dense source, identity / ReLU) in at most 96 VGPRs, so that one of its waves fits on a SIMD
+// beside the two 208-register waves of a weight-gradient block (512 registers per SIMD lane): two pixels per lane in flight
+// instead of four.  Same expressions, same pixels per thread in the same order, same tiles and LDS sums: bit-identical output.
+// gs_bn_bwd_set_form() selects it; it streams slower when it has the GPU to itself, so it is not the default.
+template <int DT, bool POOL, bool APPLY, bool GENERIC, int HEAD = 0, bool EXTRA = true, bool RN = false, bool SLIM = false>   // HEAD: 0 = tensor sources; 2 / 4 = a head of <= 2 / 4 outputs
+__global__ __launch_bounds__(256, SLIM ? 5 : 1) void bn_act_bwd_kernel(const BwdArgs a) {   // five waves per SIMD: <= 96 VGPRs
     static_assert(!HEAD || (!POOL && !GENERIC), "the head source: plain pixels, slope-family activation");
     static_assert(!(RN && GENERIC), "the rounded slope product belongs to the slope family");
+    static_assert(!SLIM || (!POOL && !GENERIC && !HEAD && !EXTRA && !RN), "the slim form: the plain U-Net launch only");
     auto mul_g = [&](float g, float d) __attribute__((always_inline)) { return RN ? mul_rn(g, d) : g * d; };
     constexpr int NH = HEAD ? HEAD : 1;
     constexpr int HEAD_CHUNK = 2048;                        // pixels whose logit gradients are staged in LDS at a time
@@ -271,7 +283,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_kernel(const BwdArgs a) {
     const int u0 = tile * a.tile_units;
     int u1 = u0 + a.tile_units < units ? u0 + a.tile_units : units;
     if (ul >= unit_lanes) u1 = u0;   // leftover threads (256 % lanes_per_unit) only join the barriers
-    constexpr int UNR = 4;           // plain path: four pixels per lane in flight (the head source with eight: no faster)
+    constexpr int UNR = SLIM ? 2 : 4;   // plain path: four pixels per lane in flight (the head source with eight: no faster)
 
     for (int ch = chl; ch - chl < nch; ch += lanes_per_unit) {      // uniform trip count: the block barriers below
         const bool ch_ok = ch < nch;
@@ -683,6 +695,16 @@ extern "C" int gs_bn_bwd_tiles(int N, int H, int W) {
     return (int)cdiv64(units, bwd_tile_units(units));
 }
 
+// Which form the plain launches (one dense source, identity / ReLU, no pool, no head) take: 0 = the normal kernel, 1 = the
+// slim one (SLIM above) for launches that run beside a weight gradient on another stream.  Every other launch ignores it.
+// A process-wide switch in the style of gs_conv3x3_set_kernel_form(): the caller sets it around the launches it means.
+static int g_bwd_form = 0;
+extern "C" int gs_bn_bwd_set_form(int form) {
+    GS_CHECK_ARG(form == 0 || form == 1, "gs_bn_bwd_set_form: form must be 0 (normal) or 1 (slim)");
+    g_bwd_form = form;
+    return GS_OK;
+}
+
 static int launch_bwd(const BwdArgs& a0, bool apply, int dtype, hipStream_t s, int* ntiles_out) {
     BwdArgs a = a0;
     a.rev = (bn_traversal() >> (apply ? 2 : 1)) & 1;
@@ -705,6 +727,10 @@ static int launch_bwd(const BwdArgs& a0, bool apply, int dtype, hipStream_t s, i
         } else if (a.dzb != nullptr || a.keep != nullptr) {                                             \
             if (apply) bn_act_bwd_kernel<DT, false, true, G, 0, true, R><<<ntiles, 256, 0, s>>>(a);     \
             else bn_act_bwd_kernel<DT, false, false, G, 0, true, R><<<ntiles, 256, 0, s>>>(a);          \
+        } else if (g_bwd_form == 1 && !(G) && !(R)) {   /* slim: S is false where the form does not exist */ \
+            constexpr bool S = !(G) && !(R);                                                            \
+            if (apply) bn_act_bwd_kernel<DT, false, true, G, 0, false, R, S><<<ntiles, 256, 0, s>>>(a); \
+            else bn_act_bwd_kernel<DT, false, false, G, 0, false, R, S><<<ntiles, 256, 0, s>>>(a);      \
         } else {                                                                                        \
             if (apply) bn_act_bwd_kernel<DT, false, true, G, 0, false, R><<<ntiles, 256, 0, s>>>(a);    \
             else bn_act_bwd_kernel<DT, false, false, G, 0, false, R><<<ntiles, 256, 0, s>>>(a);         \

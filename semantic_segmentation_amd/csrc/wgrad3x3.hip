@@ -833,6 +833,10 @@ extern "C" int gs_wgrad_reduce_unpack(const float* ws, int nparts, float* grad, 
     return GS_OK;
 }
 
+extern "C" int gs_conv3x3_wgrad_family(int W, int Cout) {
+    return w3_use_co128(W, Cout) ? 2 : (w3_use_dma(W) ? 1 : 0);
+}
+
 extern "C" int gs_conv3x3_wgrad_parts(int N, int H, int W, int Cin, int Cout) {
     return w3_ksplit(N, H, W, Cin, Cout, nullptr, nullptr, w3_use_dma(W));
 }

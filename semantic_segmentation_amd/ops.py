@@ -4,6 +4,7 @@ current HIP stream only; all arithmetic happens in libgsseg_hip.so."""
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes
 import os
 from typing import List, Optional, Sequence, Tuple
@@ -501,6 +502,11 @@ def conv3x3_wgrad_parts(N, H, W, Cin, Cout) -> int:
     return int(_lib.load().gs_conv3x3_wgrad_parts(N, H, W, Cin, Cout))
 
 
+def conv3x3_wgrad_family(W, Cout) -> int:
+    """Kernel of the 3x3 weight gradient for this shape: 0 register-staged (W < 24), 1 LDS-DMA, 2 its 128-cout form."""
+    return int(_lib.load().gs_conv3x3_wgrad_family(W, Cout))
+
+
 def conv3x3_wgrad_ws_floats(N, H, W, Cin, Cout) -> int:
     return int(_lib.load().gs_conv3x3_wgrad_ws_floats(N, H, W, Cin, Cout))
 
@@ -831,6 +837,34 @@ def bn_bwd_tiles(N, H, W) -> int:
 
 def bn_bwd_tiles_used(N, H, W, pooled: bool) -> int:
     return _lib.load().gs_bn_bwd_tiles_used(N, H, W, int(pooled))
+
+
+BN_BWD_NORMAL, BN_BWD_SLIM = 0, 1
+
+
+def bn_bwd_set_form(form: int = BN_BWD_NORMAL) -> None:
+    """Form of the plain bn_act_bwd_reduce / bn_act_bwd_apply launches (dz_a only, identity / ReLU, no pool): BN_BWD_SLIM
+    is the <= 96-VGPR kernel that fits on a CU beside a weight-gradient block of another stream (bit-identical output)."""
+    _lib.call("gs_bn_bwd_set_form", int(form))
+
+
+def bn_set_traversal(mask: int = -1) -> None:
+    """Tail-first traversal of the BatchNorm passes (bit mask: 1 forward apply, 2 backward reduce, 4 backward apply); -1 = the
+    GSSEG_BN_REV environment value.  Results do not depend on it."""
+    _lib.call("gs_bn_set_traversal", int(mask))
+
+
+@contextlib.contextmanager
+def bn_bwd_form(form: int):
+    """bn_bwd_set_form(form) around a block of launches; the normal form again afterwards (nothing to do for the normal form)."""
+    if form == BN_BWD_NORMAL:
+        yield
+        return
+    bn_bwd_set_form(form)
+    try:
+        yield
+    finally:
+        bn_bwd_set_form(BN_BWD_NORMAL)
 
 
 def bn_act_bwd_reduce(y, dz_a, sa, ca, dzp, scale, shift, mean, invstd, act, partials, dz_b=None, act_b=ACT_NONE,

@@ -31,10 +31,11 @@ from ..engine_common import ParamIndex, _flush_nbt, bn_coeffs, compute_dtype, pa
 
 # eval-mode forward without a graph: fold BatchNorm into the conv weights (GSSEG_FOLD_BN=0 keeps the two-pass form)
 FOLD_BN_INFERENCE = os.environ.get("GSSEG_FOLD_BN", "1") != "0"
-# Weight gradients on a second HIP stream (opt-in, GSSEG_WGRAD_STREAM=1): +1.6 % on the bs=32 256^2 step (14.00 -> 13.78 ms),
-# but concurrent kernels stretch each other's event-bracketed durations (conv3x3 5.67 -> 5.83 ms "per kernel"), so the
-# per-kernel roofline figures of bench.py / rocprof stop being clean: the headline runs single-stream.
-WGRAD_SIDE_STREAM = os.environ.get("GSSEG_WGRAD_STREAM", "0") != "0"
+# Weight gradients of levels 1-4 and of the transposed convolutions on a second HIP stream, launched BEHIND their stage's
+# data gradient so that they run beside the BatchNorm backward of the next stage.  Concurrent kernels
+# stretch each other's event-bracketed durations, so per-kernel roofline figures are taken with GSSEG_WGRAD_STREAM=0, which
+# keeps everything on one stream.  A stream that is being captured always gets the one-stream form.
+WGRAD_SIDE_STREAM = os.environ.get("GSSEG_WGRAD_STREAM", "1") != "0"
 # ConvTranspose2d bias gradients out of the epilogue sums of the data-gradient convolution that writes d(concat), instead of
 # a column-sum pass over that tensor (un-padded case; GSSEG_UP_BIAS_FUSED=0 restores the pass).
 # Stem backward (one input channel, image without gradient): BatchNorm backward apply + weight gradient in one pass
@@ -172,6 +173,7 @@ class UNetEngine(ParamIndex):
         # announced as soon as they are final (so the RCCL all-reduce overlaps the rest of backward), and
         # `after_backward` makes the compute stream wait for the collectives.
         self.grad_ready_hook: Optional[Callable[[str, torch.Tensor], None]] = None
+        self.last_backward_streams = 0     # streams the last backward() used: 2 = weight gradients on the side stream
         self.grad_alloc: Optional[Callable[[str, torch.Tensor], torch.Tensor]] = None
         self.after_backward: Optional[Callable[[], None]] = None
         self.grad_fetch: Optional[Callable[[str], torch.Tensor]] = None      # reduced gradient handed to autograd
@@ -913,15 +915,26 @@ class UNetEngine(ParamIndex):
             if self.grad_ready_hook is not None:
                 self.grad_ready_hook(name, g)
 
-        # The MFMA weight gradients (and their ordered slab reductions) run on a SECOND stream: nothing downstream in the
-        # backward pass needs them, so they overlap the HBM-bound BatchNorm passes of the next stage on the main stream
-        # (the BatchNorm kernels take no LDS and few registers and share the CUs with the 8-wave MFMA blocks).  dY is
-        # handed over with an event; tensors the side stream reads are recorded on it (caching allocator); the main stream
-        # joins at the end.  With a gradient-ready hook (bucketed all-reduce) a weight gradient is announced one stage
-        # later, after the main stream has waited for its event.  GSSEG_WGRAD_STREAM=0 keeps everything on one stream.
+        # The MFMA weight gradients of levels 1-4 and of the transposed convolutions (with their ordered slab reductions) run
+        # on a SECOND stream: nothing downstream in the backward pass needs them.  A stage launches its data gradient on the
+        # main stream FIRST and hands the weight gradient over behind it, so the weight gradient of stage L runs while the
+        # main stream does reduce / coeffs / apply of stage L-1 (launched in front of the data gradient, both persistent
+        # MFMA grids, it would be finished before any BatchNorm kernel starts).  A 128-cout weight-gradient block keeps two
+        # 208-register waves on every SIMD, which leaves 96 of the 512 registers: the BatchNorm kernels only become
+        # co-resident in their slim form (ops.bn_bwd_set_form, <= 96 VGPRs), taken exactly while such a weight gradient is
+        # the last thing handed to the side stream; the normal forms (109-172 VGPRs) wait for a CU to drain.  Level 0 (the
+        # 64-cout LDS-DMA kernel leaves 80 registers and streams ~5 TB/s itself) stays on the main stream.  dY is handed
+        # over with an event; tensors the side stream reads are recorded on it (caching allocator); wg_ws is touched on the
+        # main stream only after a join; the main stream joins at the end.  With a gradient-ready hook (bucketed
+        # all-reduce) a weight gradient is announced one stage later, after the main stream has waited for its event.
+        # GSSEG_WGRAD_STREAM=0 keeps everything on one stream, and so does a stream under capture (graphs keep their shape).
         main_stream = torch.cuda.current_stream(dev)
-        side = self._side_stream(dev) if WGRAD_SIDE_STREAM else None
+        two_streams = WGRAD_SIDE_STREAM and not torch.cuda.is_current_stream_capturing()
+        self.last_backward_streams = 2 if two_streams else 1
+        side = self._side_stream(dev) if two_streams else None
         deferred = []                # (name, grad, event) of side-stream gradients not yet announced
+        side_busy = [False]          # something was handed to the side stream since the last join
+        slim_bn = [False]            # ... and the last of it is a weight gradient that leaves 96 registers per SIMD lane
 
         def flush_deferred(upto_all: bool):
             while deferred and (upto_all or len(deferred) > 1):
@@ -929,12 +942,22 @@ class UNetEngine(ParamIndex):
                 main_stream.wait_event(ev)
                 emit(name, g)
 
-        def on_side(inputs, fn, name, g):
-            """run fn() (launches that read `inputs`, already complete on the main stream, and write g) on the side stream"""
-            if side is None:
+        def join_side():
+            """the main stream waits for everything handed to the side stream (before it touches wg_ws itself)"""
+            if side is not None and side_busy[0]:
+                flush_deferred(True)
+                main_stream.wait_stream(side)
+                side_busy[0] = slim_bn[0] = False
+
+        def on_side(inputs, fn, name, g, beside=True, leaves_96=False):
+            """run fn() (launches that read `inputs`, already complete on the main stream, and write g) on the side stream;
+            beside=False: on the main stream, after a join.  leaves_96: see slim_bn"""
+            if side is None or not beside:
+                join_side()
                 fn()
                 emit(name, g)
                 return
+            side_busy[0], slim_bn[0] = True, leaves_96
             ev = torch.cuda.Event()
             ev.record(main_stream)
             for t_ in inputs:
@@ -1075,10 +1098,12 @@ class UNetEngine(ParamIndex):
                 ops.conv_smallcin_fwd(rec.inp, wst, None, y_re, None, 3, 1, 1)
                 rec.y = y_re
             ntiles = ops.bn_bwd_tiles_used(N, h, w, pooled)
+            slim = slim_bn[0] and not pooled and head is None       # plain launches beside a pending weight gradient
             if head is not None:
                 ops.bn_act_bwd_reduce_head(rec.y, head[0], head[1], coef[0], coef[1], coef[2], coef[3], ACT_RELU, partials)
             else:
-                ops.bn_act_bwd_reduce(rec.y, dz_a, sa, ca, dzp, coef[0], coef[1], coef[2], coef[3], ACT_RELU, partials)
+                with ops.bn_bwd_form(ops.BN_BWD_SLIM if slim else ops.BN_BWD_NORMAL):
+                    ops.bn_act_bwd_reduce(rec.y, dz_a, sa, ca, dzp, coef[0], coef[1], coef[2], coef[3], ACT_RELU, partials)
             dgamma = galloc(rec.bnkey + ".weight", params[rec.bnkey + ".weight"])
             dbeta = galloc(rec.bnkey + ".bias", params[rec.bnkey + ".bias"])
             c12 = empty(2, cout, dtype=torch.float32)
@@ -1102,8 +1127,9 @@ class UNetEngine(ParamIndex):
             if head is not None:
                 ops.bn_act_bwd_apply_head(rec.y, head[0], head[1], coef[0], coef[1], coef[2], coef[3], c12[0], c12[1], ACT_RELU, dy)
             else:
-                ops.bn_act_bwd_apply(rec.y, dz_a, sa, ca, dzp, coef[0], coef[1], coef[2], coef[3], c12[0], c12[1],
-                                     ACT_RELU, True, dy)
+                with ops.bn_bwd_form(ops.BN_BWD_SLIM if slim else ops.BN_BWD_NORMAL):
+                    ops.bn_act_bwd_apply(rec.y, dz_a, sa, ca, dzp, coef[0], coef[1], coef[2], coef[3], c12[0], c12[1],
+                                         ACT_RELU, True, dy)
             dinp = None
             if rec.inp_is_image:
                 dw = dw_stem if dw_stem is not None else galloc(rec.wkey, wparam, zero=True)
@@ -1114,6 +1140,7 @@ class UNetEngine(ParamIndex):
             elif getattr(rec, "wide", 0):
                 # the image stage of a wide input: the weight gradient over the zero-padded channels, then the real ones
                 dwp = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=dev)
+                join_side()                                   # wg_ws on the main stream
                 ops.conv3x3_wgrad_det(rec.inp, dy, wg_ws, dwp, N, h, w, cin, cout, inv_s)
                 dw = galloc(rec.wkey, wparam)
                 dw.copy_(dwp[:, :rec.wide])
@@ -1127,12 +1154,7 @@ class UNetEngine(ParamIndex):
             else:
                 dw = galloc(rec.wkey, wparam)
                 wgrad_on_side = rec.name in det_recs
-                if wgrad_on_side:
-                    # split-K parts in slabs + ordered reduction fused with scale / unpack: deterministic, no atomics
-                    on_side((rec.inp, dy, wg_ws, dw),
-                            lambda: ops.conv3x3_wgrad_det(rec.inp, dy, wg_ws, dw, N, h, w, cin, cout, inv_s, in_stride=rec.inp_stride),
-                            rec.wkey, dw)
-                else:
+                if not wgrad_on_side:
                     dwp = dw_take(wparam.numel())
                     if ops.USE_HALO_CONV and cin % 8 == 0 and cout % 8 == 0:
                         ops.conv3x3_wgrad(rec.inp, dy, dwp, N, h, w, cin, cout, in_stride=rec.inp_stride)
@@ -1156,6 +1178,13 @@ class UNetEngine(ParamIndex):
                         ops.conv3x3(dy, rec.wd, dinp, N, h, w, cout, cin, ops.TAPS3_DGRAD)
                     else:
                         ops.conv_igemm(ops.geom_conv_dgrad_s1(N, h, w, cin, cout, 3, 1), dy, rec.wd, dinp)
+                if wgrad_on_side:
+                    # split-K parts in slabs + ordered reduction fused with scale / unpack: deterministic, no atomics.
+                    # Behind the data gradient (see `side` above); the 64-cout LDS-DMA kernel (level 0) on the main stream
+                    fam = ops.conv3x3_wgrad_family(w, cout)
+                    on_side((rec.inp, dy, wg_ws, dw),
+                            lambda: ops.conv3x3_wgrad_det(rec.inp, dy, wg_ws, dw, N, h, w, cin, cout, inv_s, in_stride=rec.inp_stride),
+                            rec.wkey, dw, beside=fam != 1, leaves_96=True)
             if rec.inp_is_image or not wgrad_on_side:
                 emit(rec.wkey, dw)
             emit(rec.bnkey + ".weight", dgamma)
@@ -1193,15 +1222,16 @@ class UNetEngine(ParamIndex):
                 db = galloc(prefix + ".up.bias", params[prefix + ".up.bias"])
                 ops.colsum(dcat, 2 * cout_t, cout_t, N, u.H2, u.W2, u.pt, u.pl, 2 * u.h, 2 * u.w, cout_t, inv_s, col_ws, db)
             dw = galloc(wkey, wparam)
+            dz = empty(N, u.h, u.w, u.cin)
+            ops.upconv2x2_dgrad(u.geom_bwd, dcat, u.wd, dz, N, u.h, u.w, u.cin, u.cout, u.H2, u.W2, 2 * cout_t, cout_t, u.pt, u.pl)
             # K = pixels pointwise GEMM on LDS-DMA operands (csrc/upwgrad.hip); the generic engine for shapes outside it.
-            # u.zin: the layer's input -- dense, or the hi plane of a pair buffer (pixel stride = its last dimension)
+            # u.zin: the layer's input -- dense, or the hi plane of a pair buffer (pixel stride = its last dimension).
+            # Behind the data gradient like the 3x3 ones; its 112-register waves leave room for the normal BatchNorm forms
             on_side((dcat, u.zin, wg_ws, dw),
                     lambda u=u, dcat=dcat, dw=dw: ops.upconv2x2_wgrad_det(
                         u.geom_wg if u.geom_wg is not None else u.geom_bwd, u.zin, dcat, wg_ws, dw, N, u.h, u.w, u.cin, u.cout,
                         u.H2, u.W2, u.zin.shape[3], 2 * u.cout, u.cout, u.pt, u.pl, inv_s),
                     wkey, dw)
-            dz = empty(N, u.h, u.w, u.cin)
-            ops.upconv2x2_dgrad(u.geom_bwd, dcat, u.wd, dz, N, u.h, u.w, u.cin, u.cout, u.H2, u.W2, 2 * cout_t, cout_t, u.pt, u.pl)
             emit(prefix + ".up.bias", db)
 
         # ---- encoder, reversed ----

@@ -140,9 +140,39 @@ def timeline(d, nsteps, out):
                                                            sum(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in last) / 1e3))
 
 
+def overlap(d, nsteps, out):
+    """BatchNorm backward against weight-gradient kernels in the LAST step: how long intervals of the two families overlap
+    (two streams), appended to `out` together with every overlapping pair"""
+    with open(find(d, "*kernel_trace.csv")) as f:
+        rows = sorted(csv.DictReader(f), key=lambda r: int(r["Start_Timestamp"]))
+    per = len(rows) // nsteps
+    last = rows[len(rows) - per:]
+    t0 = int(last[0]["Start_Timestamp"])
+    iv = lambda r: (int(r["Start_Timestamp"]), int(r["End_Timestamp"]))
+    bn = [r for r in last if "bn_act_bwd_kernel" in r["Kernel_Name"] or "bn_bwd_coeffs" in r["Kernel_Name"]]
+    wg = [r for r in last if any(k in r["Kernel_Name"] for k in ("wgrad3x3_", "upwgrad_", "wgrad_reduce"))]
+    tot, pairs = 0, []
+    for b in bn:
+        for w_ in wg:
+            o = min(iv(b)[1], iv(w_)[1]) - max(iv(b)[0], iv(w_)[0])
+            if o > 0:
+                tot += o
+                pairs.append((iv(b)[0], o, b, w_))
+    with open(out, "a") as f:
+        f.write("# BatchNorm backward x weight gradient: %d overlapping pairs, %.1f us overlapped (BatchNorm backward total %.1f us, "
+                "weight gradient total %.1f us)\n" % (len(pairs), tot / 1e3, sum(iv(r)[1] - iv(r)[0] for r in bn) / 1e3,
+                                                     sum(iv(r)[1] - iv(r)[0] for r in wg) / 1e3))
+        for s_, o, b, w_ in sorted(pairs, key=lambda p: p[0]):
+            f.write("#   at %9.1f us: %6.1f us of %s (%.1f us) inside %s (%.1f us)\n" % (
+                (s_ - t0) / 1e3, o / 1e3, short(b["Kernel_Name"])[:60], (iv(b)[1] - iv(b)[0]) / 1e3,
+                short(w_["Kernel_Name"])[:40], (iv(w_)[1] - iv(w_)[0]) / 1e3))
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "timeline":
         timeline(sys.argv[2], int(sys.argv[3]), sys.argv[4])
+    elif sys.argv[1] == "overlap":
+        overlap(sys.argv[2], int(sys.argv[3]), sys.argv[4])
     elif sys.argv[1] == "stats":
         stats(sys.argv[2], int(sys.argv[3]), sys.argv[4])
     elif sys.argv[1] == "mfma":
