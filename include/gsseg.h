@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GS_ABI_VERSION 53
+#define GS_ABI_VERSION 54
 
 enum GsDtype { GS_F16 = 0, GS_BF16 = 1 };
 enum GsStatus { GS_OK = 0, GS_EINVAL = -1, GS_ELAUNCH = -2, GS_EUNSUPPORTED = -3 };
@@ -593,6 +593,20 @@ int gs_head1x1_wide_bwd(const void* z, const float* w, const float* dl, void* dz
                         int W, int ncls, float gscale, int dtype, void* stream);
 int gs_head1x1_wide_fwd(const void* x, const float* w, const float* bias, float* y, int N, int H, int W, int ncls, int dtype,
                         void* stream);
+/* Label maps for inference.  The reference forms them from stored logits: torch.argmax(logits, 1) in
+ * GenSeg-3D/train_unet.py:39 (validation of UNet3D) and sigmoid > 0.5 / argmax in unet/evaluate.py:29-40.
+ * gs_head1x1_labels: the pair head of gs_head1x1_fwd_split / gs_head1x1_bn_fwd_split (the same kernels, the same class sums) with a
+ *   label epilogue in place of the logit stores: x_hi / x_lo dense [M][64] pair (scale / shift / act on the load path, or both NULL:
+ *   x is an activation pair), w fp32 [ncls][64], bias fp32 [ncls] or NULL -> labels uint8 [M] in the order of the input pixels
+ *   (a [NB*D, H, W] slice stack IS [NB, D, H, W]).  The label is what the predicate of gs_eval_dice gives on the logits those
+ *   kernels would have stored, bit for bit: one class 1 / (1 + expf(-x)) > 0.5 (a logit of exactly 0 -> 0); several classes the FIRST
+ *   maximum (replaced only on a strict v > best: ties go to the lowest class index).  No logits tensor is written.
+ *   x_hi / x_lo 16-byte aligned, M + 2^21 < 2^31, 1 <= ncls <= 64, dtype f16 / bf16: GS_EINVAL before any launch otherwise.
+ * gs_labels_from_logits: the same predicate on stored fp32 NCHW logits [N][C][HW] -> uint8 [N][HW], any 1 <= C <= 256 (a label is a
+ *   byte: GS_EINVAL above) -- for the engines whose head is not the pair head. */
+int gs_head1x1_labels(const void* x_hi, const void* x_lo, const float* scale, const float* shift, int act, const float* w,
+                      const float* bias, uint8_t* labels, int64_t M, int ncls, int dtype, void* stream);
+int gs_labels_from_logits(const float* logits, uint8_t* labels, int N, int C, int64_t HW, void* stream);
 /* The first conv of the pair forward for any input channel count: DoubleConv's Conv2d(n_channels, 64, 3, padding=1)
  * (unet/unet_model.py:8-24, unet/unet_parts.py:16) with n_channels > 4, and the first Conv3d of UNet3D
  * (GenSeg-3D/UNet3D/unet3d.py:89-126 with in_channels > 1) as a 2-D conv over in_channels * 3 depth-unfolded slices.

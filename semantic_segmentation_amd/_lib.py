@@ -18,7 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 GS_F16, GS_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LEAKY02, ACT_TANH = 0, 1, 2, 3
 GS_MAX_TAPS = 64
-ABI_VERSION = 53
+ABI_VERSION = 54
 
 
 class GsConvGeom(ctypes.Structure):
@@ -188,6 +188,8 @@ PROTOTYPES = {
     "gs_head1x1_wide_bwd": (c_int, [_P, _F, _F, _P, _F, _F, _F] + [c_int] * 4 + [c_float, c_int, c_void_p]),
     "gs_head1x1_wide_fwd": (c_int, [_P, _F, _F, _F] + [c_int] * 5 + [c_void_p]),
     "gs_head1x1_bn_fwd_split": (c_int, [_P, _P, _F, _F, c_int, _F, _F, _F] + [c_int] * 6 + [c_void_p]),
+    "gs_head1x1_labels": (c_int, [_P, _P, _F, _F, c_int, _F, _F, _P, c_int64, c_int, c_int, c_void_p]),
+    "gs_labels_from_logits": (c_int, [_F, _P, c_int, c_int, c_int64, c_void_p]),
     "gs_stem_fwd_bn_pair": (c_int, [_F, _F, _F, _F, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "gs_stem_bwd_onepass_strided": (c_int, [_F, _P, c_int, _P, c_int, c_int, c_int, _F, _F, c_int, c_int, c_int, c_int, c_void_p]),
     "gs_mean_loss_bwd": (c_int, [_F, _F, c_float, c_int, c_int64, _F, c_float, _F, c_void_p]),

@@ -563,6 +563,7 @@ struct HeadSArgs {
     int N, HW, Cout;
     const float* scale = nullptr; const float* shift = nullptr;      // BatchNorm + activation on the load path (x = a conv output pair)
     int act = GS_ACT_NONE;
+    uint8_t* lab = nullptr;                                          // LAB flavours: one label byte per pixel instead of the logits in y
 };
 
 __device__ __forceinline__ float sum8_dpp_p(float v) {
@@ -572,7 +573,10 @@ __device__ __forceinline__ float sum8_dpp_p(float v) {
     return v;
 }
 
-template <int DT>
+// LAB = true (gs_head1x1_labels): the label of the pixel leaves instead of its logits -- sigmoid(logit) > 0.5 for one class, else the
+// first maximum over the classes (the predicate of eval_dice_kernel, loss.hip) on exactly the values s[c] + bv[c] that the
+// logit flavour stores; lane 0 of the pixel writes the byte.
+template <int DT, bool LAB = false>
 __global__ __launch_bounds__(256) void head1x1_split_kernel(const HeadSArgs a) {
     const int ch = threadIdx.x & 7, pl = threadIdx.x >> 3;
     float w[4][8], bv[4];
@@ -606,10 +610,25 @@ __global__ __launch_bounds__(256) void head1x1_split_kernel(const HeadSArgs a) {
             s[c] = sum8_dpp_p(t);
         }
         if (ch == 0) {
-            const int n = m / a.HW, hw = m - n * a.HW;
+            if constexpr (LAB) {
+                float best = s[0] + bv[0];
+                int pred = 0;
+                if (a.Cout == 1) {
+                    pred = 1.f / (1.f + expf(-best)) > 0.5f ? 1 : 0;
+                } else {
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (c < a.Cout) a.y[((int64_t)n * a.Cout + c) * a.HW + hw] = s[c] + bv[c];
+                    for (int c = 1; c < 4; ++c) {
+                        const float v = s[c] + bv[c];
+                        if (c < a.Cout && v > best) { best = v; pred = c; }
+                    }
+                }
+                a.lab[m] = (uint8_t)pred;
+            } else {
+                const int n = m / a.HW, hw = m - n * a.HW;
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (c < a.Cout) a.y[((int64_t)n * a.Cout + c) * a.HW + hw] = s[c] + bv[c];
+            }
         }
     }
 }
@@ -619,7 +638,9 @@ __global__ __launch_bounds__(256) void head1x1_split_kernel(const HeadSArgs a) {
 // [ci][classes padded to 4] and are read at wave-uniform addresses, four classes at a time in registers.  Each class is the sum of
 // eight 8-term chains added as a tree, the order of head1x1_split_kernel.  Logit stores are coalesced along the pixel.
 // LO = false: the input is a single 16-bit plane (the 16-bit engines' head, gs_head1x1_wide_fwd) -- x_lo is never read.
-template <int DT, bool LO = true>
+// LAB = true (gs_head1x1_labels, 5..64 classes): the running first maximum of the values the logit flavour stores, one byte per
+// thread = per pixel at the end (coalesced along the pixel).
+template <int DT, bool LO = true, bool LAB = false>
 __global__ __launch_bounds__(256) void head1x1_wide_split_kernel(const HeadSArgs a) {
     __shared__ __attribute__((aligned(16))) float wl[64 * 64];
     __shared__ float bl[64], scl[64], shl[64];
@@ -656,8 +677,13 @@ __global__ __launch_bounds__(256) void head1x1_wide_split_kernel(const HeadSArgs
                 v[j * 8 + i] = t;
             }
         }
-        const int n = m / a.HW, hw = m - n * a.HW;
-        float* yp = a.y + (int64_t)n * a.Cout * a.HW + hw;
+        float* yp = nullptr;
+        if constexpr (!LAB) {
+            const int n = m / a.HW, hw = m - n * a.HW;
+            yp = a.y + (int64_t)n * a.Cout * a.HW + hw;
+        }
+        float best = 0.f;
+        int pred = 0;
         for (int c0 = 0; c0 < a.Cout; c0 += 4) {
             float t[8][4];
 #pragma unroll
@@ -677,9 +703,37 @@ __global__ __launch_bounds__(256) void head1x1_wide_split_kernel(const HeadSArgs
             for (int c = 0; c < 4; ++c)
                 if (c0 + c < a.Cout) {
                     const float s = ((t[0][c] + t[1][c]) + (t[2][c] + t[3][c])) + ((t[4][c] + t[5][c]) + (t[6][c] + t[7][c]));
-                    yp[(int64_t)(c0 + c) * a.HW] = s + bl[c0 + c];
+                    if constexpr (LAB) {
+                        const float lv = s + bl[c0 + c];
+                        if (c0 + c == 0) best = lv;
+                        else if (lv > best) { best = lv; pred = c0 + c; }
+                    } else {
+                        yp[(int64_t)(c0 + c) * a.HW] = s + bl[c0 + c];
+                    }
                 }
         }
+        if constexpr (LAB) a.lab[m] = (uint8_t)pred;
+    }
+}
+
+// ---- labels from stored fp32 NCHW logits (the engines whose head is not the pair head): one thread per pixel, the class planes
+// are read coalesced along the pixel; the predicate of eval_dice_kernel (loss.hip)
+__global__ __launch_bounds__(256) void labels_from_logits_kernel(const float* __restrict__ x, uint8_t* __restrict__ lab, int64_t total,
+                                                                 int C, int64_t HW) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t n = i / HW, hw = i - n * HW;
+        const float* xp = x + n * C * HW + hw;
+        float best = xp[0];
+        int pred = 0;
+        if (C == 1) {
+            pred = 1.f / (1.f + expf(-best)) > 0.5f ? 1 : 0;
+        } else {
+            for (int c = 1; c < C; ++c) {
+                const float v = xp[(int64_t)c * HW];
+                if (v > best) { best = v; pred = c; }
+            }
+        }
+        lab[i] = (uint8_t)pred;
     }
 }
 
@@ -952,5 +1006,47 @@ extern "C" int gs_head1x1_wide_fwd(const void* x, const float* w, const float* b
     if (dtype == GS_F16) head1x1_wide_split_kernel<GS_F16, false><<<(int)wb, 256, 0, s>>>(a);
     else head1x1_wide_split_kernel<GS_BF16, false><<<(int)wb, 256, 0, s>>>(a);
     GS_CHECK_LAUNCH("gs_head1x1_wide_fwd");
+    return GS_OK;
+}
+
+// Labels straight from the pair head (GenSeg-3D/train_unet.py:39 torch.argmax(logits, 1); unet/evaluate.py:29-40 sigmoid > 0.5 / argmax):
+// the class sums of gs_head1x1_fwd_split / gs_head1x1_bn_fwd_split with a label epilogue -- no logits tensor exists.
+extern "C" int gs_head1x1_labels(const void* x_hi, const void* x_lo, const float* scale, const float* shift, int act, const float* w,
+                                 const float* bias, uint8_t* labels, int64_t M, int ncls, int dtype, void* stream) {
+    GS_CHECK_ARG(x_hi && x_lo && w && labels && M > 0, "gs_head1x1_labels: bad arguments");
+    GS_CHECK_ARG(ncls >= 1 && ncls <= 64, "gs_head1x1_labels: ncls=%d must be 1..64", ncls);
+    GS_CHECK_ARG((((uintptr_t)x_hi | (uintptr_t)x_lo) & 15) == 0, "gs_head1x1_labels: x_hi / x_lo must be 16-byte aligned");
+    GS_CHECK_ARG(M + 8192 * 256 < 2147483647LL, "gs_head1x1_labels: too many pixels");
+    GS_CHECK_ARG(dtype == GS_F16 || dtype == GS_BF16, "gs_head1x1_labels: bad dtype");
+    GS_CHECK_ARG((scale == nullptr) == (shift == nullptr), "gs_head1x1_labels: scale / shift must both be given or NULL");
+    GS_CHECK_ARG(act == GS_ACT_NONE || act == GS_ACT_RELU || act == GS_ACT_LEAKY02, "gs_head1x1_labels: activation %d", act);
+    HeadSArgs a{(const unsigned short*)x_hi, (const unsigned short*)x_lo, w, bias, nullptr, 1, (int)M, ncls};
+    a.scale = scale; a.shift = shift; a.act = act; a.lab = labels;
+    hipStream_t s = (hipStream_t)stream;
+    if (ncls > 4) {
+        int64_t wb = cdiv64(M, 256);
+        if (wb > 8192) wb = 8192;
+        if (dtype == GS_F16) head1x1_wide_split_kernel<GS_F16, true, true><<<(int)wb, 256, 0, s>>>(a);
+        else head1x1_wide_split_kernel<GS_BF16, true, true><<<(int)wb, 256, 0, s>>>(a);
+    } else {
+        int64_t hb = cdiv64(M, 32);
+        if (hb > 8192) hb = 8192;
+        if (dtype == GS_F16) head1x1_split_kernel<GS_F16, true><<<(int)hb, 256, 0, s>>>(a);
+        else head1x1_split_kernel<GS_BF16, true><<<(int)hb, 256, 0, s>>>(a);
+    }
+    GS_CHECK_LAUNCH("gs_head1x1_labels");
+    return GS_OK;
+}
+
+// The same predicate on stored fp32 NCHW logits [N, C, HW] -> uint8 [N, HW] (engines whose head is not the pair head); C <= 256: a label is a byte
+extern "C" int gs_labels_from_logits(const float* logits, uint8_t* labels, int N, int C, int64_t HW, void* stream) {
+    GS_CHECK_ARG(logits && labels && N > 0 && HW > 0, "gs_labels_from_logits: bad arguments");
+    GS_CHECK_ARG(C >= 1 && C <= 256, "gs_labels_from_logits: C=%d must be 1..256 (labels are bytes)", C);
+    GS_CHECK_ARG(HW < (1LL << 40) && (int64_t)N * HW < (1LL << 40), "gs_labels_from_logits: too many pixels");
+    const int64_t total = (int64_t)N * HW;
+    int64_t nb = cdiv64(total, 256);
+    if (nb > 8192) nb = 8192;
+    labels_from_logits_kernel<<<(int)nb, 256, 0, (hipStream_t)stream>>>(logits, labels, total, C, HW);
+    GS_CHECK_LAUNCH("gs_labels_from_logits");
     return GS_OK;
 }

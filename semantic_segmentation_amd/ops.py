@@ -1335,13 +1335,17 @@ def conv3x3_segs(x, w, y_hi, y_lo, N, H, W, K, wrap, Cin, Cout, in_stride, in_co
                    2.0 * (N * H * W * 2 * (Cin + Cout) + 9 * K * Cout))
 
 
-def conv3d3_segs(x, w, y_hi, y_lo, NB, D, H, W, K, wrap, Cin, Cout, in_stride, in_coff=0, bn_partials=None, wrap_to=0):
+def conv3d3_segs(x, w, y_hi, y_lo, NB, D, H, W, K, wrap, Cin, Cout, in_stride, in_coff=0, bn_partials=None, wrap_to=0, bias=None,
+                 act=ACT_NONE, out_stride=None, out_coff=0):
     """Conv3d(k3, p1) of the pair forward (UNet3D): conv3x3_segs with depth -- x holds `wrap` channels per voxel ([hi | lo] planes or
     a part of them), K (a multiple of 64, wrap <= K <= 2*wrap) runs over them and wraps once, w = pack_weight_segs pack
     [27][Cout][K]; Cin = the layer's channels (FLOP count only).  wrap_to: the wrapped part of K continues at this input channel (a
-    multiple of 64) instead of channel 0.  Result: dense pair y_hi / y_lo [NB*D, H, W, Cout]."""
+    multiple of 64) instead of channel 0.  Result: dense pair y_hi / y_lo [NB*D, H, W, Cout]; with out_stride / out_coff both planes are
+    views written at channel out_coff of pixels of out_stride elements.  bias (fp32 [Cout]) and act run in the epilogue (the folded
+    inference forward: conv + bias + ReLU write the z pair)."""
     _dev(x)
-    _f32(bn_partials, "bn_partials")
+    _f32(bn_partials, "bn_partials"); _f32(bias, "bias")
+    ostr = Cout if out_stride is None else out_stride
     if not (x.dtype == w.dtype == y_hi.dtype == y_lo.dtype):
         raise TypeError("conv3d3_segs: x, w, y must share one 16-bit dtype")
     if K % 64 != 0 or wrap % 64 != 0 or not (wrap <= K <= 2 * wrap) or w.numel() != 27 * Cout * K:
@@ -1353,11 +1357,11 @@ def conv3d3_segs(x, w, y_hi, y_lo, NB, D, H, W, K, wrap, Cin, Cout, in_stride, i
     if wrap_to:
         if wrap_to % 64 != 0 or wrap_to + (K - wrap) > wrap:
             raise ValueError("conv3d3_segs: wrap_to must be a multiple of 64 with wrap_to + K - wrap <= wrap")
-        _lib.call("gs_conv3d_3x3x3_precise_to", _p(x), _p(w), _p(y_hi), _p(y_lo), None, _p(bn_partials), NB, D, H, W, K, in_stride,
-                  in_coff, wrap, wrap_to, Cout, Cout, 0, dz, dy, dx, ACT_NONE, dt_code(x), _stream())
+        _lib.call("gs_conv3d_3x3x3_precise_to", _p(x), _p(w), _p(y_hi), _p(y_lo), _p(bias), _p(bn_partials), NB, D, H, W, K, in_stride,
+                  in_coff, wrap, wrap_to, Cout, ostr, out_coff, dz, dy, dx, act, dt_code(x), _stream())
     else:
-        _lib.call("gs_conv3d_3x3x3_precise", _p(x), _p(w), _p(y_hi), _p(y_lo), None, _p(bn_partials), NB, D, H, W, K, in_stride,
-                  in_coff, wrap, Cout, Cout, 0, dz, dy, dx, ACT_NONE, dt_code(x), _stream())
+        _lib.call("gs_conv3d_3x3x3_precise", _p(x), _p(w), _p(y_hi), _p(y_lo), _p(bias), _p(bn_partials), NB, D, H, W, K, in_stride,
+                  in_coff, wrap, Cout, ostr, out_coff, dz, dy, dx, act, dt_code(x), _stream())
     if ev is not None:
         TIMER.stop("conv3x3_halo_precise", ev, 2.0 * NB * D * H * W * Cout * 27 * Cin,
                    2.0 * (NB * D * H * W * 2 * (Cin + Cout) + 27 * K * Cout))
@@ -1495,6 +1499,35 @@ def head1x1_wide_fwd(x, w, bias, y):
             or w.numel() != ncls * 64 or (bias is not None and bias.numel() != ncls)):
         raise ValueError("head1x1_wide_fwd: x [N,H,W,64] dense, logits [N,ncls,H,W] with 1..64 classes, w [ncls,64], bias [ncls]")
     _lib.call("gs_head1x1_wide_fwd", _p(x), _p(w), _p(bias), _p(y), N, H, W, ncls, dt_code(x), _stream())
+
+
+def head1x1_labels(x_hi, x_lo, w, bias, labels, scale=None, shift=None, act=ACT_NONE):
+    """Labels straight from the pair head (GenSeg-3D/train_unet.py:39, unet/evaluate.py:29-40): x_hi / x_lo dense pair [..., 64]
+    (scale / shift / act: BatchNorm + activation on the load path, x = a conv-output pair), w [ncls,64], 1..64 classes -> labels uint8,
+    one per pixel in the order of the input pixels.  One class: sigmoid > 0.5; several: the first maximum.  No logits are stored."""
+    _dev(x_hi)
+    _f32(w, "w"); _f32(bias, "bias"); _f32(scale, "scale"); _f32(shift, "shift")
+    M = x_hi.numel() // 64
+    ncls = w.numel() // 64
+    if (x_hi.shape[-1] != 64 or x_lo.shape != x_hi.shape or x_lo.dtype != x_hi.dtype or not (x_hi.is_contiguous() and x_lo.is_contiguous())
+            or labels.dtype != torch.uint8 or labels.numel() != M or not labels.is_contiguous() or w.numel() != ncls * 64
+            or not w.is_contiguous() or (bias is not None and bias.numel() != ncls) or (scale is None) != (shift is None)):
+        raise ValueError("head1x1_labels: x pair [...,64] dense of one 16-bit dtype, labels uint8 with one byte per pixel, w [ncls,64], "
+                         "bias [ncls], scale / shift together")
+    _lib.call("gs_head1x1_labels", _p(x_hi), _p(x_lo), _p(scale), _p(shift), act, _p(w), _p(bias), _p(labels), M, ncls,
+              dt_code(x_hi), _stream())
+
+
+def labels_from_logits(logits, labels):
+    """The same predicate on stored fp32 NCHW logits [N,C,...] -> labels uint8 [N,...] (the engines whose head is not the pair
+    head); 1..256 classes."""
+    _dev(logits)
+    _f32(logits, "logits")
+    N, C = logits.shape[0], logits.shape[1]
+    HW = logits.numel() // max(N * C, 1)
+    if logits.dim() < 3 or not logits.is_contiguous() or labels.dtype != torch.uint8 or labels.numel() != N * HW or not labels.is_contiguous():
+        raise ValueError("labels_from_logits: logits dense fp32 [N,C,...], labels uint8 with one byte per pixel")
+    _lib.call("gs_labels_from_logits", _p(logits), _p(labels), N, C, HW, _stream())
 
 
 def head1x1_wide_bwd(z, w, dl, dz, dw, db, gscale=1.0):

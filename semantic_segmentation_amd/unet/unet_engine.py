@@ -282,7 +282,9 @@ class UNetEngine(ParamIndex):
         return wf, bias
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x: torch.Tensor, params: Dict[str, torch.Tensor], training: bool, need_grad: bool):
+    def forward(self, x: torch.Tensor, params: Dict[str, torch.Tensor], training: bool, need_grad: bool, labels: bool = False):
+        """-> (fp32 NCHW logits, backward context).  labels (UNet.predict; no graph): -> (uint8 label map [N,H,W], None) -- from the
+        pair head's label epilogue where the pair forward runs (no logits tensor), from this engine's logits elsewhere."""
         net = self.net
         if not x.is_cuda:
             raise RuntimeError("UNet (semantic_segmentation_amd) runs on the MI355X only: move the input and the "
@@ -301,11 +303,11 @@ class UNetEngine(ParamIndex):
             elif net.n_channels > 64 or net.n_classes > 64:
                 why = f"the pair forward's end kernels take up to 64 image channels and classes (got {net.n_channels}, {net.n_classes})"
             if why is None:
-                return self.forward_precise(x, params, training, need_grad)
+                return self.forward_precise(x, params, training, need_grad, labels)
             if not self.auto:
                 if ops.USE_HALO_CONV:
                     raise NotImplementedError("UNet pair forward: " + why)
-                return self.forward_precise(x, params, training, need_grad)      # (raises: no halo-reuse conv kernel)
+                return self.forward_precise(x, params, training, need_grad, labels)      # (raises: no halo-reuse conv kernel)
             if not self._warned_fallback:
                 self._warned_fallback = True
                 warnings.warn(f"UNet(precise='auto'): {why} -- running the single 16-bit engine, whose logits are about 5e-3 from "
@@ -509,6 +511,10 @@ class UNetEngine(ParamIndex):
                 ops.conv_smallcout_fwd(inp, wo[g0:g1].contiguous(), bo[g0:g1].contiguous(), tmp)
                 logits[:, g0:g1] = tmp
         _flush_nbt(nbt_pending)
+        if labels:                                 # this engine's head is not the pair head: the predicate on its logits
+            lab = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+            ops.labels_from_logits(logits, lab)
+            return lab, None
         ctx = None
         if need_grad:
             ctx = dict(recs=recs, ups=ups, x=x, z_last=inp, N=N, H=H, W=W, hs=hs, ws=ws_, C=C, training=training)
@@ -606,7 +612,7 @@ class UNetEngine(ParamIndex):
             return cin // 2
         return None
 
-    def forward_precise(self, x: torch.Tensor, params: Dict[str, torch.Tensor], training: bool, need_grad: bool):
+    def forward_precise(self, x: torch.Tensor, params: Dict[str, torch.Tensor], training: bool, need_grad: bool, labels: bool = False):
         """The pair forward: every activation and conv output travels as a PAIR of 16-bit values v = hi + lo (hi = 16-bit(v),
         lo = 16-bit(v - hi): ~22 significand bits in fp16); BatchNorm / ReLU / max-pool / the head read and write pairs.  The
         MFMA contraction of a stage runs over a K concatenation of SEGMENTS chosen by `self.plan` (exact products, one fp32
@@ -865,6 +871,17 @@ class UNetEngine(ParamIndex):
                                        cout3, 0)
                 z_last = zl_hi
 
+        if labels:
+            # UNet.predict: the same head launch with the label epilogue (gs_head1x1_labels) -- no logits tensor is allocated
+            lab = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+            wout = params["outc.conv.weight"].detach().reshape(net.n_classes, 64).contiguous()
+            if z_last is None:
+                ops.head1x1_labels(last_rec.y, y_lo_last, wout, params["outc.conv.bias"].detach(), lab, last_rec.coef[0],
+                                   last_rec.coef[1], ACT_RELU)
+            else:
+                ops.head1x1_labels(zl_hi, zl_lo, wout, params["outc.conv.bias"].detach(), lab)
+            _flush_nbt(nbt_pending)
+            return lab, None
         logits = empty(N, net.n_classes, H, W, dtype=torch.float32)
         if z_last is None:
             ops.head1x1_bn_fwd_split(last_rec.y, y_lo_last, last_rec.coef[0], last_rec.coef[1], ACT_RELU,
@@ -1294,6 +1311,12 @@ class _UNetFunction(torch.autograd.Function):
             if have:
                 torch._foreach_add_(have, new)
         return (None, None, None, None, dx if ctx.x_needs_grad else None, *out)
+
+
+def run_unet_labels(engine: UNetEngine, x: torch.Tensor) -> torch.Tensor:
+    """UNet.predict: the forward without a graph, ending in the label map (uint8 [N,H,W])"""
+    with torch.no_grad():
+        return engine.forward(x, dict(engine.param_items()), engine.net.training, False, labels=True)[0]
 
 
 def run_unet(engine: UNetEngine, x: torch.Tensor) -> torch.Tensor:

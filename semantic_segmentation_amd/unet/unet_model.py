@@ -8,7 +8,7 @@ import os
 
 import torch.nn as nn
 
-from .unet_engine import UNetEngine, run_unet
+from .unet_engine import UNetEngine, run_unet, run_unet_labels
 from .unet_parts import DoubleConv, Down, OutConv, Up
 
 
@@ -56,6 +56,13 @@ class UNet(nn.Module):
 
     def forward(self, x):
         return run_unet(self._engine, x)
+
+    def predict(self, x):
+        """Label map of `x`: torch.uint8 [N, H, W] -- sigmoid(logit) > 0.5 for one class, the arg-max over the classes (first
+        maximum) otherwise: what unet/evaluate.py:29-40 forms from the logits and what `evaluate()` counts.  Runs under
+        torch.no_grad(); BatchNorm follows `self.training` as `forward` does (the usual call is on a network in eval mode).
+        Where the pair forward runs the head writes the labels itself and no logits tensor exists."""
+        return run_unet_labels(self._engine, x)
 
     def use_checkpointing(self):
         """Kept for API parity (unet_model.py:39-49; broken upstream: it calls the *module*

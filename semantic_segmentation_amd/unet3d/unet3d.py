@@ -10,7 +10,7 @@ import os
 
 from torch import nn
 
-from .unet3d_engine import UNet3DEngine, run_unet3d
+from .unet3d_engine import UNet3DEngine, run_unet3d, run_unet3d_labels
 
 
 class Conv3DBlock(nn.Module):
@@ -76,3 +76,10 @@ class UNet3D(nn.Module):
 
     def forward(self, input):
         return run_unet3d(self._engine, input)
+
+    def predict(self, input):
+        """Label map of a volume: torch.uint8 [NB, D, H, W] -- what GenSeg-3D/train_unet.py:39 forms with torch.argmax(logits, 1) (first
+        maximum; one class: sigmoid(logit) > 0.5).  Runs under torch.no_grad(); BatchNorm follows `self.training` as `forward` does
+        (the usual call is on a network in eval mode).  Where the pair forward runs the head writes the labels itself: neither the
+        logits nor their permuted copy exist."""
+        return run_unet3d_labels(self._engine, input)

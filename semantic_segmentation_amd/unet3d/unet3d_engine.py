@@ -19,7 +19,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from .._lib import ACT_RELU
-from ..engine_common import ParamIndex, bn_coeffs, compute_dtype
+from ..engine_common import ParamIndex, bn_coeffs, compute_dtype, pack_key, pack_reuse_allowed
 
 K3 = [(kd, ky, kx) for kd in range(3) for ky in range(3) for kx in range(3)]
 
@@ -129,6 +129,9 @@ class UNet3DEngine(ParamIndex):
         self.plan = resolve_plan3d(precise, self.dtype)
         self.auto = precise == "auto"
         self._warned_fallback = False    # "auto" names its fallback to the 16-bit engine once per engine
+        # weight packs of the pair forward by stage name + kind ("|segs", "|fsegs", "|dgrad", "|up"), each (key, tensors...): reused
+        # between forwards that keep no graph until a parameter or a running statistic changes (engine_common.pack_key / pack_reuse_allowed)
+        self._packs: Dict[str, tuple] = {}
         # data-parallel hooks (parallel.GradReducer.attach): gradients announced as they become final, the compute stream
         # waits for the collectives at the end of backward, autograd receives the reduced gradients
         self.grad_ready_hook = None
@@ -141,7 +144,14 @@ class UNet3DEngine(ParamIndex):
         if self.net.s_block1.conv3.out_channels > 64:
             raise NotImplementedError(f"UNet3D: the head kernels take up to 64 classes (got {self.net.s_block1.conv3.out_channels})")
 
-    def forward(self, x, training, need_grad):
+    def invalidate_packs(self):
+        """after writes the version counters cannot see (`.data`, raw pointers)"""
+        self._packs.clear()
+
+    def forward(self, x, training, need_grad, labels=False):
+        """-> (fp32 logits [NB, ncls, D, H, W], backward context).  labels (UNet3D.predict; no graph): -> (uint8 label map
+        [NB, D, H, W], None) -- from the pair head's label epilogue where the pair forward runs (no logits tensor), from the
+        [NB*D, ncls, H, W] logits of the 16-bit engine elsewhere (no permute copy either)."""
         net, tdt = self.net, self.tdt
         if not x.is_cuda:
             raise RuntimeError("UNet3D (semantic_segmentation_amd) runs on the MI355X only (no CPU / ATen fallback)")
@@ -162,13 +172,13 @@ class UNet3DEngine(ParamIndex):
                     except NotImplementedError as e:
                         why = str(e)
                 if why is None:
-                    return self.forward_pair(x, training, need_grad)
+                    return self.forward_pair(x, training, need_grad, labels)
                 if not self._warned_fallback:
                     self._warned_fallback = True
                     warnings.warn(f"UNet3D(precise='auto'): {why} -- running the single 16-bit engine, whose logits are 2.4e-3 to "
                                   "2.9e-3 from the fp32 reference instead of 1e-3", RuntimeWarning, stacklevel=2)
             else:
-                return self.forward_pair(x, training, need_grad)
+                return self.forward_pair(x, training, need_grad, labels)
         dev = x.device
         x = x.contiguous().float()
 
@@ -303,6 +313,10 @@ class UNet3DEngine(ParamIndex):
             ops.head1x1_wide_fwd(cur, head.weight.detach().reshape(ncls, ccur).contiguous(), head.bias.detach(), l2d)
         else:
             ops.conv_smallcout_fwd(cur, head.weight.detach().reshape(ncls, ccur, 1, 1).contiguous(), head.bias.detach(), l2d)
+        if labels:                                         # [NB*D, H, W] is [NB, D, H, W]: no permute
+            lab = torch.empty((NB, D0, H0, W0), dtype=torch.uint8, device=dev)
+            ops.labels_from_logits(l2d, lab)
+            return lab, None
         logits = l2d.view(NB, D0, ncls, H0, W0).permute(0, 2, 1, 3, 4).contiguous()
         ctx = None
         if need_grad:
@@ -353,7 +367,95 @@ class UNet3DEngine(ParamIndex):
         cache[W0] = (lay, plan)
         return cache[W0]
 
-    def forward_pair(self, x, training, need_grad):
+    def _stage_bn(self, st_name: str):
+        """the BatchNorm3d behind conv stage st_name: bn1 / bn2 of an analysis block, the ONE shared bn of a decoder block (unet3d.py:70,81-82)"""
+        blk, conv = st_name.split(".")
+        return self.submodule(blk + (".bn" if blk.startswith("s_block") else ".bn" + conv[-1]))
+
+    def _prepack_segs(self, lay, need_grad: bool, conv_fwd: bool = True):
+        """Weight packs of the pair forward, cached until the Parameter is modified; every stale one re-packed in ONE launch per kind:
+        the conv stages' segment packs ("|segs": [27][Cout][K]; "q" stages: the q pack + per-cout exponents; conv_fwd=False: the folded
+        forward has its own), with need_grad the backward's 16-bit data-gradient packs ("|dgrad"), without it the transposed convs'
+        forward packs ("|up").  A forward that keeps a graph packs the transposed convs where it runs them, both directions in one
+        launch each, as it always has."""
+        items, qitems, ditems, uitems, fresh = [], [], [], [], []
+        dev = self.net.s_block1.conv3.weight.device
+        for st_name, (segs, K, _) in lay.items():
+            conv = self.submodule(st_name)
+            cout, cin = conv.out_channels, conv.in_channels
+            wkey = pack_key(conv.weight)
+            w4 = conv.weight.detach().reshape(cout, cin, 27, 1)
+            key = (wkey, segs if segs == "q" else tuple(segs))
+            ent = self._packs.get(st_name + "|segs")
+            if conv_fwd and (ent is None or ent[0] != key):
+                pack = torch.empty((27, cout, K), dtype=self.tdt, device=dev)
+                if segs == "q":
+                    wexp = torch.empty(cout, dtype=torch.int32, device=dev)
+                    qitems.append((w4, pack, wexp))
+                    fresh.append((st_name + "|segs", (key, (pack, wexp))))
+                else:
+                    items.append((w4, pack, False, segs))
+                    fresh.append((st_name + "|segs", (key, pack)))
+            ent = self._packs.get(st_name + "|dgrad")
+            if need_grad and (ent is None or ent[0] != wkey):
+                dpack = torch.empty((27, cin, cout), dtype=self.tdt, device=dev)
+                ditems.append((w4, None, dpack, False))
+                fresh.append((st_name + "|dgrad", (wkey, dpack)))
+        if not need_grad:
+            for k in (3, 2, 1):
+                up = self.submodule(f"s_block{k}.upconv1")
+                wkey = pack_key(up.weight)
+                ent = self._packs.get(f"s_block{k}.upconv1|up")
+                if ent is None or ent[0] != wkey:
+                    ccur, cu = up.in_channels, up.out_channels
+                    wf = torch.empty((8, cu, ccur), dtype=self.tdt, device=dev)
+                    uitems.append((up.weight.detach().reshape(ccur, cu, 8, 1), wf, None, True))
+                    fresh.append((f"s_block{k}.upconv1|up", (wkey, wf, None)))
+        if items:
+            ops.pack_weight_segs(items)
+        if qitems:
+            ops.pack_weight_q8(qitems)
+        if ditems:
+            ops.pack_weight_multi(ditems)
+        if uitems:
+            ops.pack_weight_multi(uitems)
+        for name, ent in fresh:
+            self._packs[name] = ent
+
+    def _prepack_segs_folded(self, lay, plan) -> bool:
+        """Inference of the pair forward: BatchNorm3d(eval) folded into the segment packs of every conv stage but the first (which
+        reads the fp32 volume) -- w' = w * gamma * rsqrt(running_var + eps) per output channel, formed in fp32 and THEN split into the
+        stage's hi / lo segments, and the bias beta + (conv_bias - running_mean) * gamma * rsqrt(running_var + eps) that the conv epilogue
+        adds in front of the ReLU (the 3-D convs have a bias and the kernel does not add it: it enters here).  Both convs of a decoder
+        block fold with the statistics of the block's one shared BatchNorm.  Cached ("|fsegs": key, pack, bias) until a Parameter or a
+        running statistic changes; every stale pack in ONE launch.  Returns False when a BatchNorm has no running statistics."""
+        items, fresh = [], []
+        for st_name, (segs, K, _) in lay.items():
+            conv, bn = self.submodule(st_name), self._stage_bn(st_name)
+            rm, rv = bn._buffers.get("running_mean"), bn._buffers.get("running_var")
+            if rm is None or rv is None:
+                return False
+            w, cb, gamma, beta = conv.weight, conv.bias, bn.weight, bn.bias
+            cout, cin = conv.out_channels, conv.in_channels
+            key = tuple(pack_key(t) for t in (w, cb, gamma, beta, rm, rv) if t is not None) + (bn.eps, plan[st_name], tuple(segs))
+            ent = self._packs.get(st_name + "|fsegs")
+            if ent is not None and ent[0] == key:
+                continue
+            with torch.no_grad():
+                sc = gamma.detach().float() * torch.rsqrt(rv.float() + bn.eps)
+                w_eff = (w.detach().float() * sc.view(-1, 1, 1, 1, 1)).reshape(cout, cin, 27, 1).contiguous()
+                mean = rm.float() if cb is None else rm.float() - cb.detach().float()
+                bias = (beta.detach().float() - mean * sc).contiguous()
+            pack = torch.empty((27, cout, K), dtype=self.tdt, device=w.device)
+            items.append((w_eff, pack, False, segs))
+            fresh.append((st_name + "|fsegs", (key, pack, bias)))
+        if items:
+            ops.pack_weight_segs(items)
+        for name, ent in fresh:
+            self._packs[name] = ent
+        return True
+
+    def forward_pair(self, x, training, need_grad, labels=False):
         """The pair forward of UNet3D (BASELINE config 5 at the north star's 1e-3 on logits; GenSeg-3D/UNet3D/unet3d.py:89-126 is
         plain fp32): every activation and conv output travels as a PAIR of 16-bit values v = hi + lo; BatchNorm / ReLU / max-pool /
         the head read and write pairs; a conv stage runs the MFMA segments of self.plan (unet_engine.forward_precise explains the
@@ -377,32 +479,18 @@ class UNet3DEngine(ParamIndex):
         def empty(*shape, dtype=tdt):
             return torch.empty(shape, dtype=dtype, device=dev)
 
-        # every stale segment pack in ONE launch
-        items, qitems, packs = [], [], {}
-        for st_name, (segs, K, _) in lay.items():
-            conv = self.submodule(st_name)
-            cout, cin = conv.out_channels, conv.in_channels
-            pack = empty(27, cout, K)
-            if segs == "q":
-                wexp = torch.empty(cout, dtype=torch.int32, device=dev)
-                qitems.append((conv.weight.detach().reshape(cout, cin, 27, 1), pack, wexp))
-                packs[st_name] = (pack, wexp)
-            else:
-                items.append((conv.weight.detach().reshape(cout, cin, 27, 1), pack, False, segs))
-                packs[st_name] = pack
-        if items:
-            ops.pack_weight_segs(items)
-        if qitems:
-            ops.pack_weight_q8(qitems)
-        dpacks = {}
-        if need_grad:                              # the backward's data-gradient packs (16-bit, as the default engine): one launch
-            ditems = []
-            for st_name in lay:
-                conv = self.submodule(st_name)
-                cout, cin = conv.out_channels, conv.in_channels
-                dpacks[st_name] = empty(27, cin, cout)
-                ditems.append((conv.weight.detach().reshape(cout, cin, 27, 1), None, dpacks[st_name], False))
-            ops.pack_weight_multi(ditems)
+        if not pack_reuse_allowed(need_grad):
+            self._packs.clear()                        # `.data` writes are invisible to the version keys
+        # inference (eval mode, no graph): BatchNorm folded into the segment packs, conv + bias + ReLU write the z pair where the
+        # BatchNorm pass would, MaxPool3d is a read-only pass over the stored skip pair (as the 2-D engine, unet_engine.forward_precise).
+        # The two-pass form stays for training, "q" plans and BatchNorm without running statistics.
+        from ..unet import unet_engine as _ue              # (GSSEG_FOLD_BN: one switch for both engines, read per call)
+        fold = (_ue.FOLD_BN_INFERENCE and not training and not need_grad and "q" not in plan.values()
+                and self._prepack_segs_folded(lay, plan))
+        # every stale pack in ONE launch per kind: segment packs, the backward's data-gradient packs (16-bit, as the default engine)
+        self._prepack_segs(lay, need_grad, conv_fwd=not fold)
+        packs = {n_: self._packs[n_ + "|segs"][1] for n_ in lay} if not fold else {}
+        dpacks = {n_: self._packs[n_ + "|dgrad"][1] for n_ in lay} if need_grad else {}
 
         stages: List[_Stage] = []
 
@@ -414,8 +502,21 @@ class UNet3DEngine(ParamIndex):
             st = _Stage()
             st.conv, st.bn, st.cin, st.cout, st.D, st.H, st.W, st.first = conv, bn, cin, cout, D, H, W, first
             st.inp, st.in_stride, st.in_coff, st.wide, st.geom, st.x3 = inp, in_stride, 0, 0, None, None
-            y_hi, y_lo = empty(NB * D, H, W, cout), empty(NB * D, H, W, cout)
             batch = training or bn.running_mean is None
+            if fold and not first:
+                # conv + folded BatchNorm + ReLU in one launch; both planes of the z pair take (z_stride, z_coff).  The kernel always stores
+                # a pair (gs_conv3d_3x3x3_precise refuses a NULL y_lo): where no consumer reads the lo plane it lands in the unused lo
+                # half of the stage's own pair buffer [hi (cout) | lo (cout)]
+                name_ = names[id(conv)]
+                _, fpack, fbias = self._packs[name_ + "|fsegs"]
+                _, K, wrap = lay[name_]
+                wto = (conv.in_channels - (wrap - conv.in_channels)) if plan[name_] == "xw-" else 0
+                ops.conv3d3_segs(inp, fpack, z_hi, z_lo if z_lo is not None else z_hi[..., cout:], NB, D, H, W, K, wrap, cin, cout,
+                                 in_stride, 0, None, wrap_to=wto, bias=fbias, act=ACT_RELU, out_stride=z_stride, out_coff=z_coff)
+                if zp is not None:                 # read-only pass over the stored pair
+                    ops.maxpool3d_fwd_pair(z_hi[..., z_coff:], z_lo[..., z_coff:], z_stride, zp[0], zp[1], zp[2], NB, D, H, W, cout)
+                return None
+            y_hi, y_lo = empty(NB * D, H, W, cout), empty(NB * D, H, W, cout)
             if first and cin > 1:
                 # a multi-channel volume (unet3d.py:103-106): the depth-unfolded view per channel, X3[nb*D + d][c*3 + kd] =
                 # x[nb][c][d + kd - 1] (zero outside), through the fp32 MFMA stem with the weight viewed as [cout, C*3, 3, 3]
@@ -496,7 +597,7 @@ class UNet3DEngine(ParamIndex):
                 s2 = stage(blk.conv2, blk.bn2, z1, 2 * cmid, cmid, D, H, W, cat, cat[..., ctot:], 2 * ctot, cup[k], z_q8=True)
             pooled = empty(NB * (D // 2), H // 2, W // 2, 2 * cout)
             nxt_conv = f"a_block{k + 1}.conv1" if k < 3 else "bottleNeck.conv1"
-            fused_pool = FUSED_POOL3D and not cat_q8 and lo_fmt(nxt_conv) != 2 and D % 2 == 0 and H % 2 == 0 and W % 2 == 0
+            fused_pool = (FUSED_POOL3D or fold) and not cat_q8 and lo_fmt(nxt_conv) != 2 and D % 2 == 0 and H % 2 == 0 and W % 2 == 0
             if not cat_q8:
                 # residual: hi plane at channels [cup, ctot), 16-bit lo plane at [ctot, ctot + cout); the pooled pair in the same pass
                 s2 = stage(blk.conv2, blk.bn2, z1, 2 * cmid, cmid, D, H, W, cat, cat[..., ctot - cup[k]:], 2 * ctot, cup[k],
@@ -524,10 +625,16 @@ class UNet3DEngine(ParamIndex):
             D, H, W = dims[k - 1]
             cu = cup[k]
             ctot = cats[k].shape[3] // 2
-            wt = sb.upconv1.weight.detach().reshape(ccur, cu, 8, 1)
-            wf = empty(8, cu, ccur)
-            wd = empty(8, ccur, cu) if need_grad else None
-            ops.pack_weight(wt, wf, wd, True)
+            ukey = pack_key(sb.upconv1.weight)
+            ent = self._packs.get(f"s_block{k}.upconv1|up")
+            if ent is not None and ent[0] == ukey and (ent[2] is not None or not need_grad):
+                wf, wd = ent[1], ent[2]
+            else:                                      # (a forward without a graph found its pack in _prepack_segs)
+                wt = sb.upconv1.weight.detach().reshape(ccur, cu, 8, 1)
+                wf = empty(8, cu, ccur)
+                wd = empty(8, ccur, cu) if need_grad else None
+                ops.pack_weight(wt, wf, wd, True)
+                self._packs[f"s_block{k}.upconv1|up"] = (ukey, wf, wd)
             # x_hi . w_hi on the LDS-DMA pointwise GEMM, hi plane only (all eight sub-voxel classes in one launch)
             ops.upconv2x2_fwd(cur, wf, sb.upconv1.bias.detach(), cats[k], NB, d, h, w, ccur, cu, D, H, W, in_stride=2 * ccur,
                               out_stride=2 * ctot, out_coff=0)
@@ -554,8 +661,16 @@ class UNet3DEngine(ParamIndex):
                 zl = empty(2, NB * D, H, W, cmid)                   # two dense planes: the head and its backward read dense tensors
                 stage(sb.conv2, sb.bn, z1, 2 * cmid, cmid, D, H, W, zl[0], zl[1], cmid, 0)
                 z_last, ccur = zl, cmid
+        if not pack_reuse_allowed(need_grad):
+            self._packs.clear()                        # nothing of this forward may be reused: the backward context holds what it reads
         head = net.s_block1.conv3
         ncls = head.out_channels
+        if labels:
+            # UNet3D.predict: the head launch with the label epilogue (gs_head1x1_labels); [NB*D, H, W] is [NB, D, H, W] -- neither the
+            # logits nor their permuted copy exist
+            lab = torch.empty((NB, D0, H0, W0), dtype=torch.uint8, device=dev)
+            ops.head1x1_labels(z_last[0], z_last[1], head.weight.detach().reshape(ncls, ccur).contiguous(), head.bias.detach(), lab)
+            return lab, None
         l2d = empty(NB * D0, ncls, H0, W0, dtype=torch.float32)
         ops.head1x1_fwd_split(z_last[0], z_last[1], head.weight.detach().reshape(ncls, ccur).contiguous(), head.bias.detach(), l2d)
         logits = l2d.view(NB, D0, ncls, H0, W0).permute(0, 2, 1, 3, 4).contiguous()
@@ -721,6 +836,12 @@ class _UNet3DFunction(torch.autograd.Function):
         out = [(fetch(n) if (fetch is not None and n in grads) else grads.get(n)) if p.requires_grad else None
                for n, p in zip(names, ctx.plist)]
         return (None, None, None, None, *out)
+
+
+def run_unet3d_labels(engine, x):
+    """UNet3D.predict: the forward without a graph, ending in the label map (uint8 [NB, D, H, W])"""
+    with torch.no_grad():
+        return engine.forward(x, engine.net.training, False, labels=True)[0]
 
 
 def run_unet3d(engine, x):
