@@ -442,7 +442,8 @@ int gs_nhwc_to_nchw(const void* src, int src_pix_stride, int src_coff, float* ds
                     float gscale, int dtype, void* stream);
 
 /* ---- losses (train_end2end_jsrt.py:136-138,181-183; util/dice_score.py:5-28; networks.py:263-281)
- * seg loss forward: logits fp32 NCHW [N,C,H,W], mask uint8 [N,H,W] (class index; {0,1} for C==1).
+ * seg loss forward: logits fp32 NCHW [N,C,H,W], mask uint8 [N,H,W] (class index; {0,1} for C==1).  C = 1..64, forward and backward.
+ *   Mask values >= C for C > 1 are outside the contract (the result is unspecified; nothing is read or written out of bounds).
  *   C==1: BCEWithLogits(mean) + 1 - dice(sigmoid(x), t) with ONE global sum over the batch;
  *   C>1 : CrossEntropy(mean) + 1 - dice(softmax(x), onehot(t)) (global sum over N*C*H*W).
  *   out[0]=loss out[1]=ce/bce out[2]=dice_loss out[3..5]=inter(2*sum p t), sum p, sum t, out[6]=1 (multiplier of the

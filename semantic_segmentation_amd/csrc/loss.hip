@@ -10,8 +10,20 @@ namespace {
 constexpr int LOSS_MAX_BLOCKS = 1024;
 constexpr float DICE_EPS = 1e-6f;
 
-__device__ __forceinline__ float softplus_neg_abs(float x) { return log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+// exp(x) for the sigmoid and softplus tails.  Under this library's -ffp-contract=fast the compiler fuses its own expf expansion
+// (ph = x * log2e; ph - rint(ph) becomes fma(x, log2e, -rint(ph)), which counts the low part of the product twice): expf is then off
+// by up to |x| * 4e-8 relative -- 1.3e-6 at x = -33, where p = exp(x) is the whole gradient of a background pixel.  Here the reduced
+// argument is written as that one fma, with the low word of log2(e) added: nothing is left to fuse.  |x| is clamped where the result
+// is 0 or inf anyway (a NaN passes through).
+__device__ __forceinline__ float exp_tail(float x) {
+    const float c = 0x1.715476p+0f, cc = 0x1.4ae0bep-26f;        // log2(e) = c + cc
+    x = x < -104.f ? -104.f : (x > 89.f ? 89.f : x);
+    const float e = rintf(x * c);
+    const float a = fmaf(x, cc, fmaf(x, c, -e));                 // x * log2(e) - e, |a| <= 1/2
+    return ldexpf(exp2f(a), (int)e);
+}
+__device__ __forceinline__ float softplus_neg_abs(float x) { return log1pf(exp_tail(-fabsf(x))); }
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + exp_tail(-x)); }
 
 // writes NS block sums to ws[s*LOSS_MAX_BLOCKS + blockIdx.x]
 template <int NS>
@@ -68,9 +80,10 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float* __restri
                 den += expf(v - mx);
                 if (c == t) xt = v;
             }
-            const float lse = mx + logf(den);
-            s[0] += lse - xt;
-            s[1] += expf(xt - lse);     // p_t = sum_c p_c * onehot_c
+            // lse - x_t and p_t without forming lse = mx + log(den): at |logits| ~ 100 its rounding (half an ulp of 100, 4e-6) is an
+            // absolute error of the pixel's term and a relative one of p_t -- with the same sign at every pixel with this maximum
+            s[0] += (mx - xt) + logf(den);
+            s[1] += expf(xt - mx) / den;    // p_t = sum_c p_c * onehot_c
             s[2] += 1.f;                // sum_c p_c
             s[3] += 1.f;                // sum_c onehot_c
         }
@@ -228,7 +241,8 @@ inline int loss_blocks(int64_t n) {
 
 extern "C" int gs_seg_loss_fwd(const float* logits, const uint8_t* mask, int N, int C, int H, int W, float* ws,
                                float* out, void* stream) {
-    GS_CHECK_ARG(logits && mask && ws && out && N > 0 && C > 0 && C <= 64 && H > 0 && W > 0, "gs_seg_loss_fwd: bad arguments");
+    GS_CHECK_ARG(logits && mask && ws && out && N > 0 && H > 0 && W > 0, "gs_seg_loss_fwd: bad arguments");
+    GS_CHECK_ARG(C >= 1 && C <= 64, "gs_seg_loss_fwd: %d classes (1..64)", C);
     hipStream_t s = (hipStream_t)stream;
     const int64_t npix = (int64_t)N * H * W;
     const int nb = loss_blocks(npix);
@@ -240,7 +254,8 @@ extern "C" int gs_seg_loss_fwd(const float* logits, const uint8_t* mask, int N, 
 
 extern "C" int gs_seg_loss_bwd(const float* logits, const uint8_t* mask, const float* out, const float* gout,
                                float gscale, float* dlogits, int N, int C, int H, int W, void* stream) {
-    GS_CHECK_ARG(logits && mask && out && dlogits && N > 0 && C > 0 && H > 0 && W > 0, "gs_seg_loss_bwd: bad arguments");
+    GS_CHECK_ARG(logits && mask && out && dlogits && N > 0 && H > 0 && W > 0, "gs_seg_loss_bwd: bad arguments");
+    GS_CHECK_ARG(C >= 1 && C <= 64, "gs_seg_loss_bwd: %d classes (1..64)", C);
     const int64_t npix = (int64_t)N * H * W;
     int64_t nb = cdiv64(npix, 256);
     if (nb > 4096) nb = 4096;

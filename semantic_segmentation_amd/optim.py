@@ -7,7 +7,9 @@ Drop-in subclasses of torch.optim.RMSprop / torch.optim.Adam: same constructor a
 layout (`step`, `square_avg`, `momentum_buffer` / `exp_avg`, `exp_avg_sq`), so checkpoints and LR schedulers are
 interchangeable; `step()` is ONE kernel launch over every parameter of every group with torch's single-tensor
 arithmetic.  Unsupported flags of the torch classes (centered, amsgrad, maximize, sparse gradients) raise.
-Parameters must be fp32 CUDA tensors: there is no CPU path.
+Parameters must be fp32 CUDA tensors: there is no CPU path.  Parameters or gradients that are contiguous views into a flat
+buffer are accepted at any element offset: a tensor whose four pointers are not all 16-byte aligned is updated element by
+element instead of four at a time, and nothing outside the views is touched (tests/test_optim_gpu.py).
 """
 from __future__ import annotations
 

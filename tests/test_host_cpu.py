@@ -40,6 +40,21 @@ def test_argument_validation_is_synchronous(lib):
     assert lib.gs_bn_partials_floats(10, 64) >= 10 * 2 * 64
 
 
+def test_seg_loss_entry_points_share_one_class_range(lib):
+    """gs_seg_loss_fwd and gs_seg_loss_bwd take 1..64 classes, both say so, and neither launches anything outside that range (the
+    pointers below are never dereferenced: the check comes first)"""
+    fake = 4096
+    for C in (0, 65, 256):
+        assert lib.gs_seg_loss_fwd(fake, fake, 1, C, 1, 1, fake, fake, None) == -1
+        msg = lib.gs_last_error()
+        assert b"gs_seg_loss_fwd" in msg and str(C).encode() in msg and b"1..64" in msg
+        assert lib.gs_seg_loss_bwd(fake, fake, fake, None, 1.0, fake, 1, C, 1, 1, None) == -1
+        msg = lib.gs_last_error()
+        assert b"gs_seg_loss_bwd" in msg and str(C).encode() in msg and b"1..64" in msg
+    hdr = open(os.path.join(ROOT, "include", "gsseg.h")).read()
+    assert "C = 1..64, forward and backward" in hdr
+
+
 def test_unet_api_surface_and_state_dict_keys():
     from oracle import oracle
     from semantic_segmentation_amd.unet import UNet

@@ -122,3 +122,84 @@ def test_fused_step_refreshes_engine_weight_packs(which):
         if mode == "eval":
             assert torch.isfinite(a).all()
             assert float((a - before).abs().max()) > 1e-4      # the step moved every weight by ~1e-3: stale packs would give `before`
+
+
+# ---------------------------------------------------------------------------------------------------------------- views into a flat buffer
+# Every tested tensor above comes from the allocator (16-byte aligned): both kernels then take their float4 path.  A parameter or a
+# gradient that is a view into a flat buffer at an element offset of 1, 2 or 3 must take the scalar path.  Sizes: below and at one
+# float4 group of a block (1024), around two groups (2048: Adam's two-groups-per-trip loop and its single-group tail), around a chunk
+# (65536) and two chunks; each size once aligned and once at an odd offset, in ONE parameter set (one launch).
+VIEW_SIZES = [1, 3, 1024, 2047, 2048, 2049, 65535, 65536, 65537, 131072]
+VIEW_GAP = 8                                                  # untouched elements between and around the views
+
+
+def _layout():
+    """(start, n) of 2 * len(VIEW_SIZES) views: size k first at a multiple of 4 elements, then at offset 1 + k % 3 from one"""
+    spans, cur = [], VIEW_GAP
+    for k, n in enumerate(VIEW_SIZES):
+        for off in (0, 1 + k % 3):
+            start = (cur + 3) // 4 * 4 + off
+            spans.append((start, n))
+            cur = start + n + VIEW_GAP
+    return spans, (cur + 3) // 4 * 4
+
+
+def _run_views(make_ref, make_fused, which, steps=3):
+    dev = torch.device("cuda:0")
+    spans, total = _layout()
+    assert {s % 4 for s, _ in spans} == {0, 1, 2, 3}
+    g = torch.Generator().manual_seed(11)
+    init = [torch.randn(n, generator=g) for _, n in spans]
+    flats = []
+
+    def views(values):
+        """the values as views into a fresh flat device buffer (the rest of it random), and that buffer"""
+        flat = torch.randn(total, generator=g).to(dev)
+        assert flat.data_ptr() % 16 == 0
+        for (s, n), v in zip(spans, values):
+            flat[s:s + n] = v.to(dev)
+        flats.append((flat, flat.clone()))
+        return [flat[s:s + n] for s, n in spans]
+
+    p_ref = [torch.nn.Parameter(v.clone()) for v in init]
+    p_gpu = [torch.nn.Parameter(v) for v in (views(init) if which == "params" else [v.clone().to(dev) for v in init])]
+    if which == "params":
+        assert all(p.data_ptr() == flats[0][0].data_ptr() + 4 * s for p, (s, _) in zip(p_gpu, spans))
+    o_ref, o_gpu = make_ref(p_ref), make_fused(p_gpu)
+    for k in range(steps):
+        gk = torch.Generator().manual_seed(200 + k)
+        grads = [torch.randn(n, generator=gk) for _, n in spans]
+        gv = views(grads) if which == "grads" else [v.to(dev) for v in grads]
+        for a, b, gc, gd in zip(p_ref, p_gpu, grads, gv):
+            a.grad, b.grad = gc.clone(), gd
+        if which == "grads":
+            assert {b.grad.data_ptr() % 16 for b in p_gpu} == {0, 4, 8, 12}
+        o_ref.step()
+        o_gpu.step()
+    torch.cuda.synchronize()
+    for i, (a, b) in enumerate(zip(p_ref, p_gpu)):
+        err = (a.detach() - b.detach().cpu()).abs().max().item()
+        assert err <= 2e-6 * max(a.detach().abs().max().item(), 1.0), (i, spans[i], err)
+    inside = torch.zeros(total, dtype=torch.bool)
+    for s, n in spans:
+        inside[s:s + n] = True
+    for flat, before in flats:                                # nothing between or around the views moved; gradient buffers not at all
+        keep = ~inside if (which == "params" and flat is flats[0][0]) else torch.ones(total, dtype=torch.bool)
+        assert torch.equal(flat.cpu().view(torch.int32)[keep], before.cpu().view(torch.int32)[keep])
+    if which == "params":
+        assert not torch.equal(flats[0][0].cpu()[inside], flats[0][1].cpu()[inside])
+
+
+@pytest.mark.parametrize("which", ["params", "grads"])
+@pytest.mark.parametrize("momentum", [0.9, 0.0])
+def test_rmsprop_unaligned_views(which, momentum):
+    from semantic_segmentation_amd.optim import RMSprop
+    _run_views(lambda p: torch.optim.RMSprop(p, lr=1e-3, weight_decay=1e-8, momentum=momentum, foreach=False),
+               lambda p: RMSprop(p, lr=1e-3, weight_decay=1e-8, momentum=momentum), which)
+
+
+@pytest.mark.parametrize("which", ["params", "grads"])
+def test_adam_unaligned_views(which):
+    from semantic_segmentation_amd.optim import Adam
+    _run_views(lambda p: torch.optim.Adam(p, lr=2e-4, betas=(0.5, 0.999), weight_decay=1e-3, foreach=False),
+               lambda p: Adam(p, lr=2e-4, betas=(0.5, 0.999), weight_decay=1e-3), which)
