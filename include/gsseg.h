@@ -720,6 +720,37 @@ int gs_optim_adam(float* const* params, const float* const* grads, float* const*
                   const float* step_scalars, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                   void* stream);
 
+/* ---- volumes of any size around UNet3D (csrc/volume.hip) -------------------------------------------------------------
+ * The reference prepares every 3-D item on the host (GenSeg-3D/transforms.py: RandomFlip x3 :33-44, NormalizeIntensity :22-30,
+ * PadToDivisible :47-60, composed in that order :69-76, validation form :90-94) and scores torch.argmax(logits, 1) against
+ * the padded mask (GenSeg-3D/train_unet.py:37-51).  All offsets are 64-bit; every check comes before any launch.
+ * gs_volume_nonzero_stats (transforms.py:25-29): x fp32 [N][per_sample] (per_sample = C*D*H*W: one statistic over all the
+ *   channels of a sample) -> stats fp64 [N][4] = {count, mean, std, 1 / (std + 1e-5)} over the voxels with x != 0.0f (IEEE compare:
+ *   -0.0 is excluded, NaN is not).  count, sum x and sum x^2 in fp64; var = (n Q - S^2) / (n (n - 1)) (unbiased, Tensor.std()).
+ *   count == 0: mean NaN; count < 2: std NaN -- what the reference computes; kept, not raised.  Per-wave shuffle, per-block
+ *   LDS, one partial row per block in ws (gs_volume_stats_ws_doubles(N) doubles), rows summed in index order by a second launch:
+ *   no atomics, runs are bit-identical.  Samples may start at any element (peeled head, float4 body, scalar tail).
+ * gs_volume_prepare (transforms.py:42-43, :29, :58-59): out fp32 [N][C][Dp][Hp][Wp]; inside the extent
+ *   out[n,c,d,h,w] = float((double(x[n,c,fd(d),fh(h),fw(w)]) - mean_n) * inv_n), fd(d) = D-1-d when bit 0 of flips[n] is set (bits 1 / 2:
+ *   H / W), everywhere else +0.0f (padding at the far end only, after normalising).  stats (the array above) NULL: an exact copy;
+ *   flips device int32 [N] or NULL; mask uint8 [N][D][H][W] -> mask_out [N][Dp][Hp][Wp] with the same flips and zero padding in the
+ *   same launch (both NULL: no mask).  out / mask_out 16-byte aligned, Dp / Hp / Wp multiples of 8 and >= D / H / W.
+ * gs_volume_restore_labels: the inverse geometry of a uint8 label map, out[n,d,h,w] = lab[n,fd(d),fh(h),fw(w)] for
+ *   lab [N][Dp][Hp][Wp] -> out [N][D][H][W] (crop + un-flip of what train_unet.py:39 forms).
+ * gs_label_sums (train_unet.py:46-47, the labels used as numbers as the reference uses them): pred / target uint8 [N][n_per]
+ *   (sharing their offset within 16 bytes) -> sums int64 [N][3] = {sum p t, sum p, sum t}; integer arithmetic throughout (exact,
+ *   order-free), per-block partial rows in ws (gs_label_sums_ws_int64(N) int64) summed by a second launch.  dice != NULL:
+ *   dice[0] = float((2 sum_n I + eps) / (sum_n P + sum_n T + eps)), formed in fp64 (train_unet.py:49). */
+int64_t gs_volume_stats_ws_doubles(int N);
+int gs_volume_nonzero_stats(const float* x, int N, int64_t per_sample, double* ws, double* stats, void* stream);
+int gs_volume_prepare(const float* x, const uint8_t* mask, const double* stats, const int32_t* flips, float* out,
+                      uint8_t* mask_out, int N, int C, int D, int H, int W, int Dp, int Hp, int Wp, void* stream);
+int gs_volume_restore_labels(const uint8_t* lab, const int32_t* flips, uint8_t* out, int N, int D, int H, int W, int Dp, int Hp,
+                             int Wp, void* stream);
+int64_t gs_label_sums_ws_int64(int N);
+int gs_label_sums(const uint8_t* pred, const uint8_t* target, int N, int64_t n_per, int64_t* ws, int64_t* sums, float* dice,
+                  double eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,12 @@ PROTOTYPES = {
     "gs_stem_fwd_bn_pair": (c_int, [_F, _F, _F, _F, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "gs_stem_bwd_onepass_strided": (c_int, [_F, _P, c_int, _P, c_int, c_int, c_int, _F, _F, c_int, c_int, c_int, c_int, c_void_p]),
     "gs_mean_loss_bwd": (c_int, [_F, _F, c_float, c_int, c_int64, _F, c_float, _F, c_void_p]),
+    "gs_volume_stats_ws_doubles": (c_int64, [c_int]),
+    "gs_volume_nonzero_stats": (c_int, [_F, c_int, c_int64, _F, _F, c_void_p]),
+    "gs_volume_prepare": (c_int, [_F, _P, _F, _P, _F, _P] + [c_int] * 8 + [c_void_p]),
+    "gs_volume_restore_labels": (c_int, [_P, _P, _P] + [c_int] * 7 + [c_void_p]),
+    "gs_label_sums_ws_int64": (c_int64, [c_int]),
+    "gs_label_sums": (c_int, [_P, _P, c_int, c_int64, _P, _P, _F, c_double, c_void_p]),
 }
 
 _lib = None

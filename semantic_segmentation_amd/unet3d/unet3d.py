@@ -83,3 +83,14 @@ class UNet3D(nn.Module):
         (the usual call is on a network in eval mode).  Where the pair forward runs the head writes the labels itself: neither the
         logits nor their permuted copy exist."""
         return run_unet3d_labels(self._engine, input)
+
+    def predict_volume(self, volume, prep=None):
+        """Label map of a raw scan of ANY size: fp32 [D,H,W], [C,D,H,W] or [N,C,D,H,W] -> torch.uint8 with the volume's own spatial
+        shape ([D,H,W]; [N,D,H,W] for a batch).  The validation transform of GenSeg-3D/transforms.py:90-94 (NormalizeIntensity over
+        the non-zero voxels, PadToDivisible(16) at the far end) on the device, `predict`, then the crop back (volume.VolumePrep;
+        `prep` defaults to VolumePrep()).  `forward` and `predict` still take only dims that are multiples of 8."""
+        from ..volume import VolumePrep
+        prep = prep if prep is not None else VolumePrep()
+        x, _, meta = prep.prepare(volume, flips=False)
+        labels = prep.restore(self.predict(x), meta)
+        return labels if meta.ndim == 5 else labels[0]
