@@ -272,8 +272,9 @@ int gs_bn_act_bwd_apply(const void* y, const void* dz_a, int sa, int coff_a, con
                         const float* c1, const float* c2, int act, int bn, void* dy, int N, int H, int W, int C,
                         int dtype, void* stream);
 /* Kernel form of the PLAIN reduce / apply launches (dz_a only, identity or ReLU, no pool, no head source): 0 = normal
- * (the default), 1 = slim: at most 96 VGPRs, so its waves fit on a SIMD beside the two waves of a weight-gradient block
- * running on another stream.  Bit-identical output; slower when nothing runs beside it.  Process-wide, like
+ * (the default), 1 = slim: at most 96 VGPRs and 40 KB of LDS (the per-channel coefficients live there), so its waves fit
+ * on a SIMD beside the two waves of a weight-gradient block running on another stream.  C <= 1024; above that form 1
+ * launches the normal kernel.  Bit-identical output.  Process-wide, like
  * gs_conv3x3_set_kernel_form(): set it around the launches it is meant for.  Every other launch ignores it. */
 int gs_bn_bwd_set_form(int form);
 /* Traversal direction of the element-wise passes, a bit mask: 1 forward apply, 2 backward reduce, 4 backward apply walk the

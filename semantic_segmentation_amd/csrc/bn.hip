@@ -253,10 +253,15 @@ struct BwdArgs {
 // registers are compiled out (145-164 VGPRs otherwise: three waves per SIMD)
 // RN: a LeakyReLU is involved, the one slope whose product rounds: g * act'(v) goes through mul_rn.  g * 0 and g * 1 are exact
 // however they are fused, so the identity / ReLU launches (every launch of the U-Nets) take RN = false and pay nothing for it.
-// SLIM: the plain U-Net form (one dense source, identity / ReLU) in at most 96 VGPRs, so that one of its waves fits on a SIMD
-// beside the two 208-register waves of a weight-gradient block (512 registers per SIMD lane): two pixels per lane in flight
-// instead of four.  Same expressions, same pixels per thread in the same order, same tiles and LDS sums: bit-identical output.
-// gs_bn_bwd_set_form() selects it; it streams slower when it has the GPU to itself, so it is not the default.
+// SLIM: the plain U-Net form (one dense source, identity / ReLU) in at most 96 VGPRs and 40 KB of LDS, so that one of its
+// waves fits on a SIMD beside the two 208-register waves of a weight-gradient block (512 registers per SIMD lane, 43,008 B of
+// LDS left).  The per-channel coefficients -- 32 (reduce) / 48 (apply) registers in the normal form, the same values in every
+// lane of a channel chunk -- live in LDS: the block loads them once and a lane reads them at the use site, a few channels at a
+// time for its SLIM_UNR pixels in flight (about one LDS byte per streamed byte).  Same expressions on the same values, same pixels
+// per thread in the same order, same tiles and LDS sums: bit-identical output.  C <= SLIM_MAXC (the host falls back to the
+// normal kernel above it).  gs_bn_bwd_set_form() selects it; it is not the default.
+constexpr int SLIM_MAXC = 1024;   // 4 (reduce, beside the 16 KB of `red`) / 6 (apply) coefficient rows of 4 KB
+constexpr int SLIM_UNR = 4;       // pixels per lane in flight
 template <int DT, bool POOL, bool APPLY, bool GENERIC, int HEAD = 0, bool EXTRA = true, bool RN = false, bool SLIM = false>   // HEAD: 0 = tensor sources; 2 / 4 = a head of <= 2 / 4 outputs
 __global__ __launch_bounds__(256, SLIM ? 5 : 1) void bn_act_bwd_kernel(const BwdArgs a) {   // five waves per SIMD: <= 96 VGPRs
     static_assert(!HEAD || (!POOL && !GENERIC), "the head source: plain pixels, slope-family activation");
@@ -267,6 +272,11 @@ __global__ __launch_bounds__(256, SLIM ? 5 : 1) void bn_act_bwd_kernel(const Bwd
     constexpr int HEAD_CHUNK = 2048;                        // pixels whose logit gradients are staged in LDS at a time
     __shared__ float hdl[HEAD ? NH * HEAD_CHUNK : 1];
     __shared__ float red[2][256 * 8 / 8][8];   // [stat][thread][8 channels] -- reduced below
+    // SLIM: [row: scale, shift, mean, invstd, c1, c2][group of SG channels of the chunk][chunk][SG] -- a lane's SG channels are
+    // one read and the lanes of a pixel read consecutive addresses (no bank conflict).  Four channels at a time in reduce; two
+    // in apply, whose six rows would take 24 registers at four
+    constexpr int SG = APPLY ? 2 : 4;
+    __shared__ float cf[SLIM ? (APPLY ? 6 : 4) * SLIM_MAXC : 1];
     const float slope_a = a.act == GS_ACT_RELU ? 0.f : (a.act == GS_ACT_LEAKY02 ? 0.2f : 1.f);
     const float slope_b = a.act_b == GS_ACT_RELU ? 0.f : (a.act_b == GS_ACT_LEAKY02 ? 0.2f : 1.f);
     auto grad_a = [&](float v) __attribute__((always_inline)) { return GENERIC ? act_grad(v, a.act) : (v > 0.f ? 1.f : slope_a); };
@@ -283,7 +293,21 @@ __global__ __launch_bounds__(256, SLIM ? 5 : 1) void bn_act_bwd_kernel(const Bwd
     const int u0 = tile * a.tile_units;
     int u1 = u0 + a.tile_units < units ? u0 + a.tile_units : units;
     if (ul >= unit_lanes) u1 = u0;   // leftover threads (256 % lanes_per_unit) only join the barriers
-    constexpr int UNR = SLIM ? 2 : 4;   // plain path: four pixels per lane in flight (the head source with eight: no faster)
+    constexpr int UNR = 4;   // plain path: four pixels per lane in flight (the head source with eight: no faster)
+    if constexpr (SLIM) {
+        for (int c = threadIdx.x; c < a.C; c += 256) {
+            const int o = (((c & 7) / SG) * (SLIM_MAXC / 8) + (c >> 3)) * SG + c % SG;
+            cf[0 * SLIM_MAXC + o] = a.scale ? a.scale[c] : 1.f;
+            cf[1 * SLIM_MAXC + o] = a.shift ? a.shift[c] : 0.f;
+            cf[2 * SLIM_MAXC + o] = a.mean ? a.mean[c] : 0.f;
+            cf[3 * SLIM_MAXC + o] = a.invstd ? a.invstd[c] : 1.f;
+            if constexpr (APPLY) {
+                cf[4 * SLIM_MAXC + o] = a.c1 ? a.c1[c] : 0.f;
+                cf[5 * SLIM_MAXC + o] = a.c2 ? a.c2[c] : 0.f;
+            }
+        }
+        __syncthreads();
+    }
 
     for (int ch = chl; ch - chl < nch; ch += lanes_per_unit) {      // uniform trip count: the block barriers below
         const bool ch_ok = ch < nch;
@@ -291,7 +315,7 @@ __global__ __launch_bounds__(256, SLIM ? 5 : 1) void bn_act_bwd_kernel(const Bwd
         if (!ch_ok) u1 = u0;
         float sc[8], sh[8], mu[8], is[8], k1[8], k2[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < (SLIM ? 0 : 8); ++i) {
             sc[i] = a.scale ? a.scale[c0 + i] : 1.f;
             sh[i] = a.shift ? a.shift[c0 + i] : 0.f;
             mu[i] = a.mean ? a.mean[c0 + i] : 0.f;
@@ -311,7 +335,64 @@ __global__ __launch_bounds__(256, SLIM ? 5 : 1) void bn_act_bwd_kernel(const Bwd
         }
         const int HWp = a.H * a.W;
 
-        if (!POOL) {
+        if constexpr (SLIM) {
+            typedef float cfv_t __attribute__((ext_vector_type(SG)));
+            const cfv_t* cfv = reinterpret_cast<const cfv_t*>(cf);
+            for (int ub = u0 + ul; ub < u1; ub += unit_lanes * SLIM_UNR) {      // (u1 = u0 for a thread that only joins the barriers)
+                uint4 ry[SLIM_UNR], rg[SLIM_UNR];
+                bool ok[SLIM_UNR];
+#pragma unroll
+                for (int k = 0; k < SLIM_UNR; ++k) {
+                    const int u = ub + k * unit_lanes;
+                    ok[k] = u < u1;
+                    const int64_t pix = ok[k] ? u : u0;
+                    ry[k] = *reinterpret_cast<const uint4*>(a.y + pix * a.C + c0);
+                    rg[k] = a.dza ? *reinterpret_cast<const uint4*>(a.dza + pix * a.sa + a.ca + c0) : make_uint4(0, 0, 0, 0);
+                }
+                // opaque in every pass: the coefficient reads stay here, at the use site, and are not hoisted out of the loop
+                // into the registers this form exists to free
+                int cl = ch;
+                asm volatile("" : "+v"(cl));
+                unsigned int ow[SLIM_UNR][4];
+#pragma unroll
+                for (int q = 0; q < 8 / SG; ++q) {                  // the lane's channels q * SG ... q * SG + SG - 1
+                    const cfv_t zero = 0.f;
+                    const cfv_t hsc = cfv[(0 * (8 / SG) + q) * (SLIM_MAXC / 8) + cl], hsh = cfv[(1 * (8 / SG) + q) * (SLIM_MAXC / 8) + cl];
+                    const cfv_t hmu = cfv[(2 * (8 / SG) + q) * (SLIM_MAXC / 8) + cl], his = cfv[(3 * (8 / SG) + q) * (SLIM_MAXC / 8) + cl];
+                    const cfv_t hk1 = APPLY ? cfv[(4 * (8 / SG) + q) * (SLIM_MAXC / 8) + cl] : zero;
+                    const cfv_t hk2 = APPLY ? cfv[(5 * (8 / SG) + q) * (SLIM_MAXC / 8) + cl] : zero;
+#pragma unroll
+                    for (int k = 0; k < SLIM_UNR; ++k) {
+                        if (!ok[k]) continue;
+                        const unsigned int wy[4] = {ry[k].x, ry[k].y, ry[k].z, ry[k].w}, wg[4] = {rg[k].x, rg[k].y, rg[k].z, rg[k].w};
+                        float out[SG];
+#pragma unroll
+                        for (int i = 0; i < SG; ++i) {
+                            const int e = q * SG + i;               // channel of the chunk: 16-bit element e of the 16 bytes
+                            const float yv = Elem<DT>::to_f((unsigned short)(e & 1 ? wy[e >> 1] >> 16 : wy[e >> 1] & 0xffffu));
+                            const float g = Elem<DT>::to_f((unsigned short)(e & 1 ? wg[e >> 1] >> 16 : wg[e >> 1] & 0xffffu));
+                            const float v = yv * hsc[i] + hsh[i];
+                            const float gh = mul_g(g, grad_a(v)) + 0.f;      // + 0.f: the normal form's absent second source (-0 -> +0)
+                            const float xh = (yv - hmu[i]) * his[i];
+                            if (APPLY) out[i] = a.bn ? hsc[i] * (gh - hk1[i] - xh * hk2[i]) : gh;
+                            else { s1[e] += gh; s2[e] += gh * xh; }
+                        }
+                        if (APPLY) {
+#pragma unroll
+                            for (int i = 0; i < SG; i += 2) ow[k][(q * SG + i) >> 1] = Elem<DT>::pack2(out[i], out[i + 1]);
+                        }
+                    }
+                }
+                if (APPLY) {
+#pragma unroll
+                    for (int k = 0; k < SLIM_UNR; ++k) {
+                        if (!ok[k]) continue;
+                        const int64_t pix = ub + k * unit_lanes;
+                        st16(a.dy + pix * a.C + c0, make_uint4(ow[k][0], ow[k][1], ow[k][2], ow[k][3]));
+                    }
+                }
+            }
+        } else if (!POOL) {
             // a unit IS a pixel: no index decomposition at all.
             // HEAD: the tile is walked in chunks of HEAD_CHUNK pixels whose logit gradients the block stages in LDS first (one
             // coalesced pass with the (image, pixel) split per loaded element) -- as scattered per-lane loads they made the
@@ -727,7 +808,7 @@ static int launch_bwd(const BwdArgs& a0, bool apply, int dtype, hipStream_t s, i
         } else if (a.dzb != nullptr || a.keep != nullptr) {                                             \
             if (apply) bn_act_bwd_kernel<DT, false, true, G, 0, true, R><<<ntiles, 256, 0, s>>>(a);     \
             else bn_act_bwd_kernel<DT, false, false, G, 0, true, R><<<ntiles, 256, 0, s>>>(a);          \
-        } else if (g_bwd_form == 1 && !(G) && !(R)) {   /* slim: S is false where the form does not exist */ \
+        } else if (g_bwd_form == 1 && !(G) && !(R) && a.C <= SLIM_MAXC) {   /* slim: S is false where the form does not exist */ \
             constexpr bool S = !(G) && !(R);                                                            \
             if (apply) bn_act_bwd_kernel<DT, false, true, G, 0, false, R, S><<<ntiles, 256, 0, s>>>(a); \
             else bn_act_bwd_kernel<DT, false, false, G, 0, false, R, S><<<ntiles, 256, 0, s>>>(a);      \

@@ -938,9 +938,11 @@ class UNetEngine(ParamIndex):
         # main stream does reduce / coeffs / apply of stage L-1 (launched in front of the data gradient, both persistent
         # MFMA grids, it would be finished before any BatchNorm kernel starts).  A 128-cout weight-gradient block keeps two
         # 208-register waves on every SIMD, which leaves 96 of the 512 registers: the BatchNorm kernels only become
-        # co-resident in their slim form (ops.bn_bwd_set_form, <= 96 VGPRs), taken exactly while such a weight gradient is
-        # the last thing handed to the side stream; the normal forms (109-172 VGPRs) wait for a CU to drain.  Level 0 (the
-        # 64-cout LDS-DMA kernel leaves 80 registers and streams ~5 TB/s itself) stays on the main stream.  dY is handed
+        # co-resident in their slim form (ops.bn_bwd_set_form, <= 96 VGPRs), taken for the plain launches of levels 1-4 from
+        # the hand-over of such a weight gradient until the next join: it may still be running behind whatever was handed over
+        # after it (in an Up block the 2C -> C weight gradient behind the transposed convolution's); the normal forms
+        # (109-172 VGPRs) wait for a CU to drain.  Level 0 (the 64-cout LDS-DMA kernel leaves 80 registers and streams
+        # ~5 TB/s itself) stays on the main stream, and its BatchNorm launches on the normal form.  dY is handed
         # over with an event; tensors the side stream reads are recorded on it (caching allocator); wg_ws is touched on the
         # main stream only after a join; the main stream joins at the end.  With a gradient-ready hook (bucketed
         # all-reduce) a weight gradient is announced one stage later, after the main stream has waited for its event.
@@ -951,7 +953,7 @@ class UNetEngine(ParamIndex):
         side = self._side_stream(dev) if two_streams else None
         deferred = []                # (name, grad, event) of side-stream gradients not yet announced
         side_busy = [False]          # something was handed to the side stream since the last join
-        slim_bn = [False]            # ... and the last of it is a weight gradient that leaves 96 registers per SIMD lane
+        slim_bn = [False]            # ... and some of it is a weight gradient that leaves 96 registers per SIMD lane
 
         def flush_deferred(upto_all: bool):
             while deferred and (upto_all or len(deferred) > 1):
@@ -974,7 +976,7 @@ class UNetEngine(ParamIndex):
                 fn()
                 emit(name, g)
                 return
-            side_busy[0], slim_bn[0] = True, leaves_96
+            side_busy[0], slim_bn[0] = True, slim_bn[0] or leaves_96
             ev = torch.cuda.Event()
             ev.record(main_stream)
             for t_ in inputs:
@@ -1115,7 +1117,8 @@ class UNetEngine(ParamIndex):
                 ops.conv_smallcin_fwd(rec.inp, wst, None, y_re, None, 3, 1, 1)
                 rec.y = y_re
             ntiles = ops.bn_bwd_tiles_used(N, h, w, pooled)
-            slim = slim_bn[0] and not pooled and head is None       # plain launches beside a pending weight gradient
+            # plain launches of levels 1-4 beside a weight gradient that may still be running
+            slim = slim_bn[0] and not pooled and head is None and (h, w) != (hs[0], ws_[0])
             if head is not None:
                 ops.bn_act_bwd_reduce_head(rec.y, head[0], head[1], coef[0], coef[1], coef[2], coef[3], ACT_RELU, partials)
             else:
