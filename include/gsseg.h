@@ -455,6 +455,30 @@ int gs_seg_loss_fwd(const float* logits, const uint8_t* mask, int N, int C, int 
                     void* stream);
 int gs_seg_loss_bwd(const float* logits, const uint8_t* mask, const float* out, const float* gout, float gscale,
                     float* dlogits, int N, int C, int H, int W, void* stream);
+/* Class-weighted cross-entropy, the criterion of both 3-D scripts: GenSeg-3D/train_unet.py:135,155,170 build
+ * CrossEntropyLoss(weight=torch.Tensor(BCE_WEIGHTS)), GenSeg-3D/UNet3D/config.py:35 sets BCE_WEIGHTS = [0.004, 0.996],
+ * GenSeg-3D/train_end2end.py:139,189,203,215 use the same criterion.  logits fp32 [N][C][S] (S = voxels of a sample, any spatial
+ * rank flattened), target uint8 [N][S], weight fp32 [C] or NULL (all ones).  2 <= C <= 64, N >= 1, S >= 1, else GS_EINVAL
+ * before any launch.  Targets >= C are outside the contract (the result is unspecified; nothing is read or written out of bounds).
+ * forward: loss = sum_i w[t_i] (lse_i - x_{i,t_i}) / sum_i w[t_i] (torch's weighted mean).  out[0] = loss, out[1] = the numerator,
+ *   out[2] = W = sum_i w[t_i], out[3] = 1 (gradient multiplier), out[4..7] = 0; out has 8 floats.  W == 0 gives out[0] = NaN as
+ *   torch does (the gradient is then outside the contract).  labels != NULL: also the arg-max class of every voxel, uint8 [N][S],
+ *   the first maximum (replaced only on a strict v > best, as gs_eval_dice / gs_labels_from_logits), from the loads the loss
+ *   makes anyway.  ws: gs_wce_ws_floats() floats.  Per-block partial rows summed by one block in double, no atomics: two runs
+ *   give the same bits.
+ * backward: dlogits (OVERWRITE) [i,c] = gout[0] * gscale * out[3] * w[t_i] * (p_{i,c} - [c == t_i]) / out[2] (gout: device scalar or
+ *   NULL = 1).
+ * data-parallel: a caller that all-reduces out[1] and out[2], rewrites out[0] = out[1] / out[2] and out[2], and sets out[3] = world
+ *   gets the exact global-batch weighted mean from the gradient AVERAGE over the ranks (per-rank means of a weighted loss are not
+ *   the global mean: W differs per rank).
+ * 16-byte accesses, four voxels per thread, when S % 4 == 0 and logits / dlogits are 16-byte and target / labels 4-byte aligned;
+ * one voxel per thread otherwise.  Grid: min(1024, ceil(items / 256)) forward, min(2048, ceil(items / 256)) backward, items =
+ * N * S / 4 or N * S. */
+int64_t gs_wce_ws_floats(void);
+int gs_wce_fwd(const float* logits, const uint8_t* target, const float* weight, int N, int C, int64_t S, float* ws, float* out,
+               uint8_t* labels, void* stream);
+int gs_wce_bwd(const float* logits, const uint8_t* target, const float* weight, const float* out, const float* gout, float gscale,
+               float* dlogits, int N, int C, int64_t S, void* stream);
 /* generic dice_loss(input, target) on fp32 tensors of n elements, one global sum (dice_score.py:25-28 with
  * reduce_batch_first=True): out[0]=loss, out[1..3]=inter,sum_p,sum_t.  bwd: dinput = dloss/dinput * gout[0]. */
 /* Per-item Dice coefficients in ONE launch pair (util/dice_score.py:5-17 with reduce_batch_first=False, the form

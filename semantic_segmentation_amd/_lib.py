@@ -199,6 +199,9 @@ PROTOTYPES = {
     "gs_volume_restore_labels": (c_int, [_P, _P, _P] + [c_int] * 7 + [c_void_p]),
     "gs_label_sums_ws_int64": (c_int64, [c_int]),
     "gs_label_sums": (c_int, [_P, _P, c_int, c_int64, _P, _P, _F, c_double, c_void_p]),
+    "gs_wce_ws_floats": (c_int64, []),
+    "gs_wce_fwd": (c_int, [_F, _P, _F, c_int, c_int, c_int64, _F, _F, _P, c_void_p]),
+    "gs_wce_bwd": (c_int, [_F, _P, _F, _F, _F, c_float, _F, c_int, c_int, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -583,3 +583,280 @@ extern "C" int gs_mean_loss_bwd(const float* x, const float* t, float cval, int 
     GS_CHECK_LAUNCH("gs_mean_loss_bwd");
     return GS_OK;
 }
+
+// ---- class-weighted cross-entropy (GenSeg-3D/train_unet.py:135,155,170; UNet3D/config.py:35; train_end2end.py:139,189,203,215) ----
+// loss = sum_i w[t_i] (lse_i - x_{i,t_i}) / sum_i w[t_i] over logits fp32 [N][C][S], target uint8 [N][S]; the arg-max label map on
+// request from the same loads.  One pass over the logits in either direction.
+//
+// Work items.  Vector path (S % 4 == 0 and logits / dlogits 16-byte, target / labels 4-byte aligned: every class plane of every
+// sample then starts on a 16-byte boundary): one item = four consecutive voxels of a sample, one 16-byte load per class plane,
+// one 4-byte load of the target, 16-byte stores.  Scalar path (anything else -- with S % 4 != 0 the planes of one voxel sit at
+// different offsets within 16 bytes, so no head peel aligns them all): one item = one voxel, 4-byte accesses coalesced along the
+// wave; it needs no head or tail because nothing in it is wider than an element.
+//   items = N * S / 4 (vector) or N * S (scalar)
+//   forward grid  = min(WCE_FWD_MAX_BLOCKS = 1024, ceil(items / 256)) blocks of 256 threads, grid-stride over the items;
+//                   capped above 1 048 576 voxels (vector) / 262 144 (scalar)
+//   backward grid = min(WCE_BWD_MAX_BLOCKS = 2048, ceil(items / 256)); capped above 2 097 152 voxels (vector) / 524 288 (scalar)
+// Classes.  C = 2, 3, 4 are compile-time: a voxel's C logits stay in registers, one read per pass.  C = 5..64: running maximum and
+// rescaled sum (one exp per class), x_t and the arg-max picked up in the same loop, so the forward still reads each logit once; the
+// backward reads the row a second time (the lines were fetched a moment ago by the same thread).
+// Reduction: per-thread fp32 -> wave -> block -> ws[2][1024] rows -> one finalising block in double, in a fixed order: no atomics,
+// two runs give the same bits.  The weights sit in LDS; the index into them is clamped (targets >= C are outside the contract).
+constexpr int WCE_FWD_MAX_BLOCKS = LOSS_MAX_BLOCKS;
+constexpr int WCE_BWD_MAX_BLOCKS = 2048;
+
+namespace {
+
+template <int V>
+__device__ __forceinline__ void wce_load(const float* __restrict__ p, float (&v)[V]) {
+    if constexpr (V == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+        v[0] = p[0];
+    }
+}
+template <int V>
+__device__ __forceinline__ void wce_store(float* __restrict__ p, const float (&v)[V]) {
+    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else p[0] = v[0];
+}
+template <int V>
+__device__ __forceinline__ void wce_load_u8(const uint8_t* __restrict__ p, int (&t)[V]) {
+    if constexpr (V == 4) {
+        const uchar4 q = *reinterpret_cast<const uchar4*>(p);
+        t[0] = q.x; t[1] = q.y; t[2] = q.z; t[3] = q.w;
+    } else {
+        t[0] = p[0];
+    }
+}
+template <int V>
+__device__ __forceinline__ void wce_store_u8(uint8_t* __restrict__ p, const int (&t)[V]) {
+    if constexpr (V == 4) *reinterpret_cast<uchar4*>(p) = make_uchar4((uint8_t)t[0], (uint8_t)t[1], (uint8_t)t[2], (uint8_t)t[3]);
+    else p[0] = (uint8_t)t[0];
+}
+
+// item -> (sample, first voxel); a 32-bit division wherever the item count allows (uniform branch)
+__device__ __forceinline__ void wce_split(int64_t i, int64_t per, bool small, int64_t& n, int64_t& r) {
+    if (small) {
+        const uint32_t q = (uint32_t)i / (uint32_t)per;
+        n = q; r = (uint32_t)i - q * (uint32_t)per;
+    } else {
+        n = i / per; r = i - n * per;
+    }
+}
+
+// the weights of a block in LDS (ones without a weight vector); C <= 64
+__device__ __forceinline__ void wce_stage_weights(const float* __restrict__ w, int C, float* wl) {
+    if (threadIdx.x < 64) wl[threadIdx.x] = (w && (int)threadIdx.x < C) ? w[threadIdx.x] : 1.f;
+    __syncthreads();
+}
+
+// running maximum and the sum of exp(x - maximum) of one more value: one exp per value
+__device__ __forceinline__ void wce_online(float v, float& mx, float& den) {
+    const float d = v - mx;
+    const float e = exp_tail(-fabsf(d));
+    den = d <= 0.f ? den + e : fmaf(den, e, 1.f);
+    mx = fmaxf(mx, v);
+}
+
+// CR: the class count when it is 2, 3 or 4 (registers), 0 = any count at run time.  V: voxels per item (4 or 1).
+template <int CR, int V>
+__global__ __launch_bounds__(256) void wce_fwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ tg,
+                                                      const float* __restrict__ w, int N, int Crt, int64_t S, float* ws,
+                                                      uint8_t* __restrict__ labels) {
+    __shared__ float wl[64];
+    const int C = CR ? CR : Crt;
+    wce_stage_weights(w, C, wl);
+    const int64_t per = S / V, items = (int64_t)N * per;
+    const bool small = items < (1LL << 32);
+    float s[2] = {0.f, 0.f};                                    // sum w_t (lse - x_t), sum w_t
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (int64_t)gridDim.x * 256) {
+        int64_t n, r;
+        wce_split(i, per, small, n, r);
+        const int64_t s0 = r * V;
+        const float* xp = x + n * C * S + s0;
+        int t[V], pred[V];
+        wce_load_u8<V>(tg + n * S + s0, t);
+        float mx[V], den[V], xt[V];
+        if constexpr (CR > 0) {
+            float v[CR][V];
+#pragma unroll
+            for (int c = 0; c < CR; ++c) wce_load<V>(xp + (int64_t)c * S, v[c]);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                float best = v[0][j];
+                pred[j] = 0; mx[j] = v[0][j]; xt[j] = 0.f; den[j] = 0.f;
+#pragma unroll
+                for (int c = 1; c < CR; ++c) {
+                    if (v[c][j] > best) { best = v[c][j]; pred[j] = c; }
+                    mx[j] = fmaxf(mx[j], v[c][j]);
+                }
+#pragma unroll
+                for (int c = 0; c < CR; ++c) {
+                    den[j] += exp_tail(v[c][j] - mx[j]);
+                    if (c == t[j]) xt[j] = v[c][j];
+                }
+            }
+        } else {
+            float v[V], best[V];
+            wce_load<V>(xp, v);
+#pragma unroll
+            for (int j = 0; j < V; ++j) { best[j] = mx[j] = v[j]; den[j] = 1.f; pred[j] = 0; xt[j] = t[j] == 0 ? v[j] : 0.f; }
+#pragma unroll 4
+            for (int c = 1; c < C; ++c) {
+                wce_load<V>(xp + (int64_t)c * S, v);
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    if (v[j] > best[j]) { best[j] = v[j]; pred[j] = c; }
+                    if (c == t[j]) xt[j] = v[j];
+                    wce_online(v[j], mx[j], den[j]);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float wt = wl[t[j] < C ? t[j] : C - 1];
+            // (mx - x_t) + log(den), not lse - x_t: the comment in seg_loss_fwd_kernel
+            s[0] = fmaf(wt, (mx[j] - xt[j]) + logf(den[j]), s[0]);
+            s[1] += wt;
+        }
+        if (labels) wce_store_u8<V>(labels + n * S + s0, pred);
+    }
+    block_store_sums<2>(s, ws);
+}
+
+__global__ __launch_bounds__(256) void wce_finalize_kernel(const float* ws, int nb, float* out) {
+    __shared__ double red[256];
+    const double num = final_sum(ws, 0, nb, red);
+    const double wsum = final_sum(ws, 1, nb, red);
+    if (threadIdx.x == 0) {
+        out[0] = (float)(num / wsum);          // 0 / 0 = NaN when every weight met is zero, as torch gives
+        out[1] = (float)num;
+        out[2] = (float)wsum;
+        out[3] = 1.f;                          // gradient multiplier (the world size when out[1], out[2] are global sums)
+        out[4] = 0.f; out[5] = 0.f; out[6] = 0.f; out[7] = 0.f;
+    }
+}
+
+template <int CR, int V>
+__global__ __launch_bounds__(256) void wce_bwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ tg,
+                                                      const float* __restrict__ w, const float* __restrict__ out,
+                                                      const float* gout, float gscale, float* __restrict__ dx, int N, int Crt,
+                                                      int64_t S) {
+    __shared__ float wl[64];
+    const int C = CR ? CR : Crt;
+    wce_stage_weights(w, C, wl);
+    const float coef = (gout ? gout[0] : 1.f) * gscale * out[3] / out[2];
+    const int64_t per = S / V, items = (int64_t)N * per;
+    const bool small = items < (1LL << 32);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (int64_t)gridDim.x * 256) {
+        int64_t n, r;
+        wce_split(i, per, small, n, r);
+        const int64_t s0 = r * V;
+        const float* xp = x + n * C * S + s0;
+        float* dp = dx + n * C * S + s0;
+        int t[V];
+        wce_load_u8<V>(tg + n * S + s0, t);
+        float g[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) g[j] = coef * wl[t[j] < C ? t[j] : C - 1];
+        if constexpr (CR > 0) {
+            float v[CR][V];
+#pragma unroll
+            for (int c = 0; c < CR; ++c) wce_load<V>(xp + (int64_t)c * S, v[c]);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                float mx = v[0][j], den = 0.f;
+#pragma unroll
+                for (int c = 1; c < CR; ++c) mx = fmaxf(mx, v[c][j]);
+#pragma unroll
+                for (int c = 0; c < CR; ++c) { v[c][j] = exp_tail(v[c][j] - mx); den += v[c][j]; }
+                const float rden = 1.f / den;
+#pragma unroll
+                for (int c = 0; c < CR; ++c) v[c][j] = g[j] * (v[c][j] * rden - (c == t[j] ? 1.f : 0.f));
+            }
+#pragma unroll
+            for (int c = 0; c < CR; ++c) wce_store<V>(dp + (int64_t)c * S, v[c]);
+        } else {
+            float v[V], mx[V], den[V];
+            wce_load<V>(xp, v);
+#pragma unroll
+            for (int j = 0; j < V; ++j) { mx[j] = v[j]; den[j] = 1.f; }
+#pragma unroll 4
+            for (int c = 1; c < C; ++c) {
+                wce_load<V>(xp + (int64_t)c * S, v);
+#pragma unroll
+                for (int j = 0; j < V; ++j) wce_online(v[j], mx[j], den[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < V; ++j) den[j] = 1.f / den[j];
+#pragma unroll 4
+            for (int c = 0; c < C; ++c) {
+                wce_load<V>(xp + (int64_t)c * S, v);
+#pragma unroll
+                for (int j = 0; j < V; ++j) v[j] = g[j] * (exp_tail(v[j] - mx[j]) * den[j] - (c == t[j] ? 1.f : 0.f));
+                wce_store<V>(dp + (int64_t)c * S, v);
+            }
+        }
+    }
+}
+
+inline int wce_blocks(int64_t items, int cap) {
+    const int64_t b = cdiv64(items, 256);
+    return (int)(b > cap ? cap : b);
+}
+
+inline bool wce_args_ok(int N, int C, int64_t S, const char* who) {
+    if (C < 2 || C > 64) { gs_set_error("%s: %d classes (2..64)", who, C); return false; }
+    if (N < 1 || S < 1 || S > (1LL << 56) / ((int64_t)N * C)) {
+        gs_set_error("%s: N=%d S=%lld (both >= 1, N*C*S < 2^56)", who, N, (long long)S);
+        return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int64_t gs_wce_ws_floats(void) { return 2 * (int64_t)LOSS_MAX_BLOCKS; }
+
+extern "C" int gs_wce_fwd(const float* logits, const uint8_t* target, const float* weight, int N, int C, int64_t S, float* ws,
+                          float* out, uint8_t* labels, void* stream) {
+    GS_CHECK_ARG(logits && target && ws && out, "gs_wce_fwd: NULL pointer");
+    if (!wce_args_ok(N, C, S, "gs_wce_fwd")) return GS_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec = S % 4 == 0 && ((uintptr_t)logits & 15) == 0 && (((uintptr_t)target | (uintptr_t)labels) & 3) == 0;
+    const int64_t items = vec ? (int64_t)N * (S / 4) : (int64_t)N * S;
+    const int nb = wce_blocks(items, WCE_FWD_MAX_BLOCKS);
+#define WCE_FWD(CR, V) wce_fwd_kernel<CR, V><<<nb, 256, 0, s>>>(logits, target, weight, N, C, S, ws, labels)
+    const int cr = C <= 4 ? C : 0;
+    if (vec) {
+        if (cr == 2) WCE_FWD(2, 4); else if (cr == 3) WCE_FWD(3, 4); else if (cr == 4) WCE_FWD(4, 4); else WCE_FWD(0, 4);
+    } else {
+        if (cr == 2) WCE_FWD(2, 1); else if (cr == 3) WCE_FWD(3, 1); else if (cr == 4) WCE_FWD(4, 1); else WCE_FWD(0, 1);
+    }
+#undef WCE_FWD
+    wce_finalize_kernel<<<1, 256, 0, s>>>(ws, nb, out);
+    GS_CHECK_LAUNCH("gs_wce_fwd");
+    return GS_OK;
+}
+
+extern "C" int gs_wce_bwd(const float* logits, const uint8_t* target, const float* weight, const float* out, const float* gout,
+                          float gscale, float* dlogits, int N, int C, int64_t S, void* stream) {
+    GS_CHECK_ARG(logits && target && out && dlogits, "gs_wce_bwd: NULL pointer");
+    if (!wce_args_ok(N, C, S, "gs_wce_bwd")) return GS_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec = S % 4 == 0 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0 && ((uintptr_t)target & 3) == 0;
+    const int64_t items = vec ? (int64_t)N * (S / 4) : (int64_t)N * S;
+    const int nb = wce_blocks(items, WCE_BWD_MAX_BLOCKS);
+#define WCE_BWD(CR, V) wce_bwd_kernel<CR, V><<<nb, 256, 0, s>>>(logits, target, weight, out, gout, gscale, dlogits, N, C, S)
+    const int cr = C <= 4 ? C : 0;
+    if (vec) {
+        if (cr == 2) WCE_BWD(2, 4); else if (cr == 3) WCE_BWD(3, 4); else if (cr == 4) WCE_BWD(4, 4); else WCE_BWD(0, 4);
+    } else {
+        if (cr == 2) WCE_BWD(2, 1); else if (cr == 3) WCE_BWD(3, 1); else if (cr == 4) WCE_BWD(4, 1); else WCE_BWD(0, 1);
+    }
+#undef WCE_BWD
+    GS_CHECK_LAUNCH("gs_wce_bwd");
+    return GS_OK;
+}

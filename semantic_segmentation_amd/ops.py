@@ -1153,6 +1153,51 @@ def seg_loss_bwd(logits, mask_u8, out, gout, gscale, dlogits):
               _stream())
 
 
+def _wce_shapes(logits, target_u8, weight, who):
+    if logits.dim() < 3:
+        raise ValueError(f"{who}: logits must be [N,C,*spatial] with at least one spatial dim, got {tuple(logits.shape)}")
+    N, C = logits.shape[0], logits.shape[1]
+    S = logits.numel() // (N * C) if N * C else 0
+    if target_u8.dtype != torch.uint8 or not target_u8.is_contiguous() or target_u8.device != logits.device:
+        raise TypeError(f"{who}: target must be contiguous uint8 [N,*spatial] on the logits' device")
+    if target_u8.numel() != N * S:
+        raise ValueError(f"{who}: target {tuple(target_u8.shape)} does not match logits {tuple(logits.shape)}")
+    if weight is not None:
+        _f32(weight, "weight")
+        if weight.numel() != C or weight.device != logits.device:
+            raise ValueError(f"{who}: weight must hold one fp32 value per class ({C}) on the logits' device")
+    return N, C, S
+
+
+def wce_ws_floats():
+    return int(_lib.load().gs_wce_ws_floats())
+
+
+def wce_fwd(logits, target_u8, weight, ws, out, labels=None):
+    """gs_wce_fwd: class-weighted cross-entropy of fp32 logits [N,C,*spatial] against uint8 targets [N,*spatial]; out[8] = loss,
+    numerator, W, 1, 0...; labels (uint8, one byte per voxel, or None): the arg-max label map from the same pass."""
+    _dev(logits)
+    _f32(logits, "logits"); _f32(ws, "ws"); _f32(out, "out")
+    N, C, S = _wce_shapes(logits, target_u8, weight, "wce_fwd")
+    if ws.numel() < wce_ws_floats() or out.numel() < 8:
+        raise ValueError("wce_fwd: ws must hold gs_wce_ws_floats() floats and out 8")
+    if labels is not None and (labels.dtype != torch.uint8 or not labels.is_contiguous() or labels.numel() != N * S
+                               or labels.device != logits.device):
+        raise TypeError("wce_fwd: labels must be contiguous uint8 with one byte per voxel on the logits' device")
+    _lib.call("gs_wce_fwd", _p(logits), _p(target_u8), _p(weight), N, C, S, _p(ws), _p(out), _p(labels), _stream())
+
+
+def wce_bwd(logits, target_u8, weight, out, gout, gscale, dlogits):
+    """gs_wce_bwd: dlogits (overwritten) = gout * gscale * out[3] * w[t] * (softmax - onehot) / out[2]; gout a device scalar or None."""
+    _dev(logits)
+    _f32(logits, "logits"); _f32(out, "out"); _f32(gout, "gout"); _f32(dlogits, "dlogits")
+    N, C, S = _wce_shapes(logits, target_u8, weight, "wce_bwd")
+    if dlogits.shape != logits.shape or dlogits.device != logits.device or out.numel() < 8:
+        raise ValueError("wce_bwd: dlogits must have the logits' shape and device, out 8 floats")
+    _lib.call("gs_wce_bwd", _p(logits), _p(target_u8), _p(weight), _p(out), _p(gout), float(gscale), _p(dlogits), N, C, S,
+              _stream())
+
+
 def dice_loss_fwd(p, t, ws, out):
     _dev(p)
     _f32(p, "input"); _f32(t, "target")
