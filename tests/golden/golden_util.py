@@ -30,16 +30,20 @@ def _normal(g, shape, std, mean=0.0):
     return torch.randn(shape, generator=g) * std + mean
 
 
-def seeded_generator_state_dict(seed: int, input_nc=1, output_nc=1, num_downs=8, ngf=64) -> Dict[str, torch.Tensor]:
+def seeded_generator_state_dict(seed: int, input_nc=1, output_nc=1, num_downs=8, ngf=64, bias_std=0.0) -> Dict[str, torch.Tensor]:
     """State dict with the 100 key names/shapes of the reference
     UnetGenerator(1,1,8,64,BatchNorm,use_dropout) (models_pix2pix/networks.py:514-617);
-    values ~ init_net 'normal' (conv N(0,0.02), BN gamma N(1,0.02), biases 0; networks.py:84-104)."""
+    values ~ init_net 'normal' (conv N(0,0.02), BN gamma N(1,0.02), biases 0; networks.py:84-104).
+    bias_std > 0: every bias ~ N(0, bias_std) instead (a trained network's; the default draws nothing for them)."""
     g = torch.Generator().manual_seed(seed)
     sd: Dict[str, torch.Tensor] = {}
 
+    def zeros(c):
+        return _normal(g, (c,), bias_std) if bias_std > 0 else torch.zeros(c)
+
     def bn(name, c):
         sd[name + ".weight"] = _normal(g, (c,), 0.02, 1.0)
-        sd[name + ".bias"] = torch.zeros(c)
+        sd[name + ".bias"] = zeros(c)
         sd[name + ".running_mean"] = torch.zeros(c)
         sd[name + ".running_var"] = torch.ones(c)
         sd[name + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.long)
@@ -48,7 +52,7 @@ def seeded_generator_state_dict(seed: int, input_nc=1, output_nc=1, num_downs=8,
         for j, k in enumerate((4, 6, 8)):
             sd[f"{name}._ops._ops.{j}.op.weight"] = _normal(g, (cin, cout, k, k), 0.02)
             if bias:
-                sd[f"{name}._ops._ops.{j}.op.bias"] = torch.zeros(cout)
+                sd[f"{name}._ops._ops.{j}.op.bias"] = zeros(cout)
 
     # (outer_nc, inner_nc) from outermost to innermost
     chans = [(output_nc, ngf), (ngf, ngf * 2), (ngf * 2, ngf * 4), (ngf * 4, ngf * 8)]
@@ -75,19 +79,27 @@ def seeded_generator_state_dict(seed: int, input_nc=1, output_nc=1, num_downs=8,
     return sd
 
 
-def seeded_discriminator_state_dict(seed: int, input_nc=2, ndf=64) -> Dict[str, torch.Tensor]:
-    """22 keys of NLayerDiscriminator(2,64,3,BatchNorm) (networks.py:620-665)."""
+def seeded_discriminator_state_dict(seed: int, input_nc=2, ndf=64, n_layers=3, bias_std=0.0) -> Dict[str, torch.Tensor]:
+    """22 keys of NLayerDiscriminator(2,64,3,BatchNorm) (networks.py:620-665); n_layers: the convs at 2, 5, ... 3 * n_layers - 1
+    (the last of them with stride 1) and the head at 3 * n_layers + 2.  bias_std as in seeded_generator_state_dict."""
     g = torch.Generator().manual_seed(seed)
     sd: Dict[str, torch.Tensor] = {}
+
+    def zeros(c):
+        return _normal(g, (c,), bias_std) if bias_std > 0 else torch.zeros(c)
+
     sd["model.0.weight"] = _normal(g, (ndf, input_nc, 4, 4), 0.02)
-    sd["model.0.bias"] = torch.zeros(ndf)
-    for conv_i, bn_i, ci, co in ((2, 3, ndf, ndf * 2), (5, 6, ndf * 2, ndf * 4), (8, 9, ndf * 4, ndf * 8)):
+    sd["model.0.bias"] = zeros(ndf)
+    mult = [min(2 ** n, 8) for n in range(n_layers + 1)]
+    for n in range(1, n_layers + 1):
+        conv_i, bn_i, ci, co = 3 * n - 1, 3 * n, ndf * mult[n - 1], ndf * mult[n]
         sd[f"model.{conv_i}.weight"] = _normal(g, (co, ci, 4, 4), 0.02)
         sd[f"model.{bn_i}.weight"] = _normal(g, (co,), 0.02, 1.0)
-        sd[f"model.{bn_i}.bias"] = torch.zeros(co)
+        sd[f"model.{bn_i}.bias"] = zeros(co)
         sd[f"model.{bn_i}.running_mean"] = torch.zeros(co)
         sd[f"model.{bn_i}.running_var"] = torch.ones(co)
         sd[f"model.{bn_i}.num_batches_tracked"] = torch.tensor(0, dtype=torch.long)
-    sd["model.11.weight"] = _normal(g, (1, ndf * 8, 4, 4), 0.02)
-    sd["model.11.bias"] = torch.zeros(1)
+    last = 3 * n_layers + 2
+    sd[f"model.{last}.weight"] = _normal(g, (1, ndf * mult[n_layers], 4, 4), 0.02)
+    sd[f"model.{last}.bias"] = zeros(1)
     return sd
