@@ -776,6 +776,34 @@ int64_t gs_label_sums_ws_int64(int N);
 int gs_label_sums(const uint8_t* pred, const uint8_t* target, int N, int64_t n_per, int64_t* ws, int64_t* sums, float* dice,
                   double eps, void* stream);
 
+/* InstanceNorm2d(affine=False, track_running_stats=False) of the Pix2Pix networks under `--norm instance`
+ * (reference options/base_options.py:36, models_pix2pix/networks.py:23-38 get_norm_layer; generator :553-617, PatchGAN :620-665;
+ * csrc/instnorm.hip).  y [N,H,W,C] dense NHWC 16-bit; statistics per (sample, channel) over the H*W plane; fp32 arrays [N][C].
+ * Every entry point: GS_EINVAL before any launch for a bad dtype, a pointer that is not 16-byte aligned (keep masks: 8), C %% 8 != 0
+ * or H*W < 2 (torch: "Expected more than 1 spatial element").  No allocation, no synchronisation, no atomics: every sum has one
+ * fixed order (two runs give equal bits).  ws: gs_in_ws_floats(N,H,W,C) floats, 16-byte aligned (0: none needed, may be NULL) --
+ * planes that are split over several blocks are joined by a second launch in slice order.
+ * gs_in_stats: mean[n][c]; invstd[n][c] = 1 / sqrt(biased variance + eps).  The variance is centred at every level (per-thread sums
+ *   about the thread's first pixel, then Chan's pairwise update in double); the mean is the plane's sum, exact in double, over H*W;
+ *   the only fp32 roundings are the two final conversions.
+ * gs_in_act_apply (networks.py:583-586,606-607,642-657): z = act((y - mean) * invstd) [* keep_mask * keep_scale] written with
+ *   (z_pix_stride, z_coff); optional second output z2 = act2((y - mean) * invstd) with its own stride / offset from the same read of y
+ *   (the generator's down path: LeakyReLU dense for the next conv, ReLU into the concat buffer; z2 takes no keep mask).
+ *   act / act2: none, ReLU, LeakyReLU(0.2).
+ * gs_in_act_bwd: with xh = (y - mean) * invstd and g = act'(xh) * keep * keep_scale * dz_a + act_b'(xh) * dz_b
+ *   (dz_a strided (sa, coff_a); dz_b optional dense second consumer; ReLU'(0) = 0, LeakyReLU'(0) = 0.2 as gs_bn_act_bwd_*):
+ *   dy = invstd * (g - mean_plane(g) - xh * mean_plane(g * xh)).  gmeans fp32 [2][N][C] receives the two plane means (each term
+ *   fp32, summed in double).  A reduce launch (+ the join) and an apply launch. */
+int64_t gs_in_ws_floats(int N, int H, int W, int C);
+int gs_in_stats(const void* y, float eps, float* mean, float* invstd, float* ws, int N, int H, int W, int C, int dtype,
+                void* stream);
+int gs_in_act_apply(const void* y, const float* mean, const float* invstd, int act, void* z, int z_pix_stride, int z_coff,
+                    const uint8_t* keep_mask, float keep_scale, void* z2, int act2, int z2_pix_stride, int z2_coff, int N, int H,
+                    int W, int C, int dtype, void* stream);
+int gs_in_act_bwd(const void* y, const float* mean, const float* invstd, const void* dz_a, int sa, int coff_a, int act,
+                  const uint8_t* keep_mask, float keep_scale, const void* dz_b, int act_b, void* dy, float* gmeans, float* ws,
+                  int N, int H, int W, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

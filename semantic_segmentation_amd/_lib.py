@@ -202,6 +202,10 @@ PROTOTYPES = {
     "gs_wce_ws_floats": (c_int64, []),
     "gs_wce_fwd": (c_int, [_F, _P, _F, c_int, c_int, c_int64, _F, _F, _P, c_void_p]),
     "gs_wce_bwd": (c_int, [_F, _P, _F, _F, _F, c_float, _F, c_int, c_int, c_int64, c_void_p]),
+    "gs_in_ws_floats": (c_int64, [c_int] * 4),
+    "gs_in_stats": (c_int, [_P, c_float, _F, _F, _F] + [c_int] * 5 + [c_void_p]),
+    "gs_in_act_apply": (c_int, [_P, _F, _F, c_int, _P, c_int, c_int, _P, c_float, _P, c_int, c_int, c_int] + [c_int] * 5 + [c_void_p]),
+    "gs_in_act_bwd": (c_int, [_P, _F, _F, _P, c_int, c_int, c_int, _P, c_float, _P, c_int, _P, _F, _F] + [c_int] * 5 + [c_void_p]),
 }
 
 _lib = None

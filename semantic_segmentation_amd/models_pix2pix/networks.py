@@ -23,7 +23,8 @@ class Identity(nn.Module):
 
 
 def get_norm_layer(norm_type='instance'):
-    """networks.py:23-41.  Only 'batch' (the pix2pix default, pix2pix_model.py:34) runs on the HIP engine."""
+    """networks.py:23-41.  'batch' (the pix2pix default, pix2pix_model.py:34) and 'instance' (the default of --norm,
+    options/base_options.py:36) run on the HIP engine."""
     if norm_type == 'batch':
         return functools.partial(nn.BatchNorm2d, affine=True, track_running_stats=True)
     if norm_type == 'instance':
@@ -139,6 +140,20 @@ def arch_parameters():
     return [upconv_arch, conv_arch]
 
 
+def _uses_instance_norm(norm_layer):
+    """the reference's `use_bias` (networks.py:572-575, :631-634): the norm layer is InstanceNorm2d.  The engine runs the
+    InstanceNorm the reference builds (affine=False, track_running_stats=False: no parameters, no buffers) and no other."""
+    func = norm_layer.func if type(norm_layer) == functools.partial else norm_layer
+    if func != nn.InstanceNorm2d:
+        return False
+    probe = norm_layer(8)
+    for flag in ("affine", "track_running_stats"):
+        if getattr(probe, flag):
+            raise NotImplementedError("InstanceNorm2d with %s=True is not on the MI355X hot path (get_norm_layer('instance') "
+                                      "builds affine=False, track_running_stats=False)" % flag)
+    return True
+
+
 class MixedOp_upconv(nn.Module):
     """networks.py:486-496: holds the three transposed-conv primitives (`_ops.{0,1,2}.op.*`)."""
 
@@ -176,12 +191,7 @@ class UnetSkipConnectionBlock(nn.Module):
         super(UnetSkipConnectionBlock, self).__init__()
         self.outermost = outermost
         self.innermost = innermost
-        if type(norm_layer) == functools.partial:
-            use_bias = norm_layer.func == nn.InstanceNorm2d
-        else:
-            use_bias = norm_layer == nn.InstanceNorm2d
-        if use_bias:
-            raise NotImplementedError("InstanceNorm generators are not on the MI355X hot path (pix2pix uses norm='batch')")
+        use_bias = _uses_instance_norm(norm_layer)
         if input_nc is None:
             input_nc = outer_nc
         downconv = nn.Conv2d(input_nc, inner_nc, kernel_size=4, stride=2, padding=1, bias=use_bias)
@@ -246,12 +256,7 @@ class NLayerDiscriminator(nn.Module):
 
     def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, compute_dtype=None):
         super(NLayerDiscriminator, self).__init__()
-        if type(norm_layer) == functools.partial:
-            use_bias = norm_layer.func == nn.InstanceNorm2d
-        else:
-            use_bias = norm_layer == nn.InstanceNorm2d
-        if use_bias:
-            raise NotImplementedError("InstanceNorm discriminators are not on the MI355X hot path")
+        use_bias = _uses_instance_norm(norm_layer)
         kw, padw = 4, 1
         sequence = [nn.Conv2d(input_nc, ndf, kernel_size=kw, stride=2, padding=padw), nn.LeakyReLU(0.2, True)]
         nf_mult = 1

@@ -4,7 +4,9 @@ Per level k the BatchNorm output feeds two consumers with different activations 
 the next down-conv through LeakyReLU(0.2) and (through the in-place-aliased skip + the parent's uprelu) the
 up-conv through ReLU; gs_bn_act_bwd_* takes both gradient sources (dz_a/act, dz_b/act_b) in one pass.
 Every merged transposed conv yields dWm (per sub-pixel class, MFMA wgrad), split into dW4/dW6/dW8 and the
-three architecture dot products (gs_upconv_split_wgrad); its data gradient is a stride-2 64-tap conv of dY."""
+three architecture dot products (gs_upconv_split_wgrad); its data gradient is a stride-2 64-tap conv of dY.
+Under InstanceNorm (a stage that saved `inorm`) gs_in_act_bwd takes the place of the three BatchNorm launches with the same
+consumers; a bias directly in front of an InstanceNorm gets exact zeros (and no share in d arch), the other biases gs_colsum."""
 from __future__ import annotations
 
 import math
@@ -45,10 +47,15 @@ def generator_backward(engine, ctx, arch, dout, need_dx):
     def emit(p, g):
         emitter.emit(names[id(p)], g)
 
-    def bn_bwd(y, coef, stats, bnmod, dz_a, sa, ca, act, dz_b=None, act_b=ACT_NONE, keep=None, kscale=1.0):
-        """gradient w.r.t. the raw conv output y of  act(bn(y)) [two consumers / dropout]; emits dgamma/dbeta."""
+    def bn_bwd(y, coef, stats, bnmod, dz_a, sa, ca, act, dz_b=None, act_b=ACT_NONE, keep=None, kscale=1.0, inorm=None):
+        """gradient w.r.t. the raw conv output y of  act(bn(y)) [two consumers / dropout]; emits dgamma/dbeta.
+        inorm: the (mean, invstd) [2,N,C] of an InstanceNorm stage (no parameters: nothing is emitted)."""
         _, h, w, C = y.shape
         dy = empty(N, h, w, C)
+        if inorm is not None:
+            ops.in_act_bwd(y, inorm[0], inorm[1], dz_a, sa, ca, act, dy, empty(2, N, C, dtype=torch.float32),
+                           ops.in_workspace(N, h, w, C, dev), dz_b=dz_b, act_b=act_b, keep_mask=keep, keep_scale=kscale)
+            return dy
         if bnmod is None:
             ops.bn_act_bwd_apply(y, dz_a, sa, ca, None, None, None, None, None, None, None, act, False, dy,
                                  dz_b=dz_b, act_b=act_b, keep_mask=keep, keep_scale=kscale)
@@ -68,6 +75,18 @@ def generator_backward(engine, ctx, arch, dout, need_dx):
         emit(bnmod.weight, dgamma)
         emit(bnmod.bias, dbeta)
         return dy
+
+    def bias_grad(conv, dy, cancelled):
+        """gradient of a down conv's bias: exact zeros where an InstanceNorm follows (the bias cancels), else column sums of dy"""
+        if conv.bias is None:
+            return
+        if cancelled:
+            emit(conv.bias, torch.zeros_like(conv.bias))
+            return
+        _, h, w, C = dy.shape
+        db = empty(C, dtype=torch.float32)
+        ops.colsum(dy, C, 0, N, h, w, 0, 0, h, w, C, inv_s, empty(1024 * C, dtype=torch.float32), db)
+        emit(conv.bias, db)
 
     def upconv_bwd(d, du, cpad):
         """du: gradient w.r.t. the merged transposed conv output [N,2h,2w,cpad]; returns dR[d+1]."""
@@ -108,7 +127,11 @@ def generator_backward(engine, ctx, arch, dout, need_dx):
                                w8.detach().contiguous(), sm, inv_s, dw4, dw6, dw8, dots, nparts=nparts if direct else 1)
         emit(w4, dw4); emit(w6, dw6); emit(w8, dw8)
         b0 = cell._ops._ops[0].op.bias
-        if b0 is not None:                                     # merged bias = sum_j sm_j b_j
+        if b0 is not None and info.get("inorm") is not None:   # in front of an InstanceNorm: cancelled, no share in d arch
+            for j in range(3):
+                bj = cell._ops._ops[j].op.bias
+                emit(bj, torch.zeros_like(bj))
+        elif b0 is not None:                                   # merged bias = sum_j sm_j b_j
             colws = empty(1024 * cpad, dtype=torch.float32)
             dbm = empty(cpad, dtype=torch.float32)
             ops.colsum(du, cpad, 0, N, 2 * h, 2 * w, 0, 0, 2 * h, 2 * w, cpad, inv_s, colws, dbm)
@@ -142,7 +165,7 @@ def generator_backward(engine, ctx, arch, dout, need_dx):
         upnorm = parts[d][3]
         src = dR_levels[d]                                        # [N,h_d,w_d,2c_d]; second half belongs to block d
         du = bn_bwd(info["u"], info["coef"], info["stats"], upnorm, src, 2 * c[d], c[d], ACT_RELU,
-                    keep=info["keep"], kscale=info["kscale"])
+                    keep=info["keep"], kscale=info["kscale"], inorm=info.get("inorm"))
         dR_levels[d + 1] = upconv_bwd(d, du, info["cout"])
 
     # ---- down path, innermost first ------------------------------------------------------------------
@@ -156,7 +179,8 @@ def generator_backward(engine, ctx, arch, dout, need_dx):
             dy = bn_bwd(lv["y"], lv["coef"], lv["stats"], downnorm, src, c[k], 0, ACT_RELU)
         else:
             dy = bn_bwd(lv["y"], lv["coef"], lv["stats"], downnorm, src, 2 * c[k], 0, ACT_RELU,
-                        dz_b=dL, act_b=ACT_LEAKY02)
+                        dz_b=dL, act_b=ACT_LEAKY02, inorm=lv.get("inorm"))
+        bias_grad(conv, dy, lv.get("inorm") is not None)
         if k == 1:
             dw = torch.zeros_like(conv.weight, memory_format=torch.contiguous_format)
             ops.conv_smallcin_wgrad(ctx["x"], dy, dw, 4, 2, 1, inv_s)

@@ -11,7 +11,13 @@ Generator (reference models_pix2pix/networks.py:514-617, 8 levels at 256x256):
     transposed conv (exact; csrc/pix2pix.hip), split into 4 sub-pixel classes of 16 taps on the MFMA engine;
     BN (+dropout keep-mask) + ReLU write into the second half of R_{k-1}.
 Discriminator (:620-665): direct 2->64 conv, three MFMA convs with BN+LeakyReLU, direct 512->1 head (fp32 logits).
-Gradients are carried multiplied by a power-of-two scale (see unet_engine.py)."""
+Gradients are carried multiplied by a power-of-two scale (see unet_engine.py).
+`--norm instance` (InstanceNorm2d without parameters or running statistics, networks.py:23-38): the same plans with the norm's
+statistics per (sample, channel) from gs_in_stats after each normed conv (train and eval alike) and gs_in_act_apply in place of
+gs_bn_act_apply -- on the down path ONE pass writes both consumers.  The reference's convs then carry a bias: one directly in front
+of an InstanceNorm cancels exactly in the norm, so the conv does not add it and its gradient is exact zeros (as the 3-D engine does
+for BatchNorm, engine_common.bn_coeffs); the others (outermost / innermost down conv, image cell, the PatchGAN's first and last
+conv) go through the convs' bias arguments and gs_colsum."""
 from __future__ import annotations
 
 import math
@@ -23,6 +29,22 @@ import torch
 from .. import ops
 from .._lib import ACT_LEAKY02, ACT_NONE, ACT_RELU, ACT_TANH
 from ..engine_common import ParamIndex, _flush_nbt, bn_coeffs, compute_dtype, pack_key, pack_reuse_allowed
+
+
+def is_instance_norm(m):
+    return isinstance(m, torch.nn.InstanceNorm2d)
+
+
+def instance_stats(y, norm):
+    """[2, N, C] fp32 (mean, invstd) of the stored conv output y [N,H,W,C] per (sample, channel): gs_in_stats"""
+    N, H, W, C = y.shape
+    mi = torch.empty((2, N, C), dtype=torch.float32, device=y.device)
+    ops.in_stats(y, norm.eps, mi[0], mi[1], ops.in_workspace(N, H, W, C, y.device))
+    return mi
+
+
+def _bias32(conv):
+    return None if conv.bias is None else conv.bias.detach().float().contiguous()
 
 
 def _need_cuda(x):
@@ -146,7 +168,7 @@ class GeneratorEngine(ParamIndex):
                 conv = m
             elif n == "Cell_upconv":
                 cell = m
-            elif n == "BatchNorm2d":
+            elif n in ("BatchNorm2d", "InstanceNorm2d"):
                 norms.append(m)
             elif n == "Dropout":
                 drop = m
@@ -199,7 +221,7 @@ class GeneratorEngine(ParamIndex):
         # ---- down path -------------------------------------------------------------------------------
         conv0 = parts[0][0]
         y1 = empty(N, hs[1], ws[1], c[1])
-        ops.conv_smallcin_fwd(x, conv0.weight.detach().contiguous(), None, y1, None, 4, 2, 1)
+        ops.conv_smallcin_fwd(x, conv0.weight.detach().contiguous(), _bias32(conv0), y1, None, 4, 2, 1)
         L[1] = empty(N, hs[1], ws[1], c[1])
         R[1] = empty(N, hs[1], ws[1], 2 * c[1])
         ops.bn_act_apply(y1, None, None, ACT_LEAKY02, L[1], c[1], 0)
@@ -211,11 +233,19 @@ class GeneratorEngine(ParamIndex):
                                     lambda conv=conv: self._pack_conv(conv.weight))
             g = cached_geom(ops.geom_conv, N, hs[k - 1], ws[k - 1], c[k - 1], c[k], 4, 2, 1)
             y = empty(N, hs[k], ws[k], c[k])
+            if is_instance_norm(downnorm):                           # (never the innermost level: that one has no norm)
+                ops.conv_igemm(g, L[k - 1], wf, y, None, None)       # the conv's bias cancels in the norm: not added
+                mi = instance_stats(y, downnorm)
+                ctx["levels"][k] = dict(y=y, coef=None, stats=True, inorm=mi, geom=g, wd=wd, inp=L[k - 1])
+                L[k] = empty(N, hs[k], ws[k], c[k])
+                R[k] = empty(N, hs[k], ws[k], 2 * c[k])
+                ops.in_act_apply(y, mi[0], mi[1], ACT_LEAKY02, L[k], c[k], 0, z2=R[k], act2=ACT_RELU, z2_stride=2 * c[k], z2_coff=0)
+                continue
             has_bn = downnorm is not None
             mt = ops.conv_igemm_mtiles(g)
             use_stats = has_bn and (training or downnorm.running_mean is None)
             part = empty(ops.bn_partials_numel(mt, c[k]), dtype=torch.float32) if use_stats else None
-            ops.conv_igemm(g, L[k - 1], wf, y, None, part)
+            ops.conv_igemm(g, L[k - 1], wf, y, None if has_bn else _bias32(conv), part)
             coef, stats = (None, False)
             if has_bn:
                 coef, stats = bn_coeffs(downnorm, part, mt, c[k], N * hs[k] * ws[k], training, dev, nbt_pending)
@@ -246,12 +276,13 @@ class GeneratorEngine(ParamIndex):
             h, w = hs[d + 1], ws[d + 1]
             H2, W2 = 2 * h, 2 * w
             bias = None
-            if cell._ops._ops[0].op.bias is not None:
+            inorm = d > 0 and is_instance_norm(upnorm)
+            if cell._ops._ops[0].op.bias is not None and not inorm:       # (in front of an InstanceNorm the bias cancels)
                 bias = sum(sm[j] * cell._ops._ops[j].op.bias.detach() for j in range(3)).float().contiguous()
             if d > 0:
                 u = empty(N, H2, W2, cout_t)
                 mt = ops.conv_igemm_mtiles(cached_geom(ops.geom_convT_class, N, h, w, cin_t, cout_t, 8, 3, 0, 0, identity_slots=True))
-                use_stats = training or upnorm.running_mean is None
+                use_stats = not inorm and (training or upnorm.running_mean is None)
                 part = empty(ops.bn_partials_numel(4 * mt, cout_t), dtype=torch.float32) if use_stats else None
                 geoms = []
                 for cls in range(4):
@@ -259,7 +290,10 @@ class GeneratorEngine(ParamIndex):
                 pslices = [part[cls * mt * 2 * cout_t:] for cls in range(4)] if part is not None else None
                 # the four sub-pixel classes in ONE launch (each is latency bound on its own at the script's batch size)
                 ops.conv_igemm_batch(geoms, R[d + 1], [pf[cls] for cls in range(4)], u, bias, pslices)
-                coef, stats = bn_coeffs(upnorm, part, 4 * mt, cout_t, N * H2 * W2, training, dev, nbt_pending)
+                if inorm:
+                    coef, stats, mi = None, True, instance_stats(u, upnorm)
+                else:
+                    coef, stats = bn_coeffs(upnorm, part, 4 * mt, cout_t, N * H2 * W2, training, dev, nbt_pending)
                 keep, kscale = None, 1.0
                 if drop is not None and training and drop.p > 0:
                     if dropout_masks is not None:
@@ -269,9 +303,14 @@ class GeneratorEngine(ParamIndex):
                     kscale = 1.0 / (1.0 - drop.p)
                 if drop is not None:
                     mask_i += 1
-                ops.bn_act_apply(u, coef[0], coef[1], ACT_RELU, R[d], 2 * c[d], c[d], None, keep, kscale)
+                if inorm:
+                    ops.in_act_apply(u, mi[0], mi[1], ACT_RELU, R[d], 2 * c[d], c[d], keep, kscale)
+                else:
+                    ops.bn_act_apply(u, coef[0], coef[1], ACT_RELU, R[d], 2 * c[d], c[d], None, keep, kscale)
                 ctx["ups"][d] = dict(u=u, coef=coef, stats=stats, keep=keep, kscale=kscale, sm=sm, cin=cin_t,
                                      cout=cout_t, li=li)
+                if inorm:
+                    ctx["ups"][d]["inorm"] = mi
             else:                                                    # outermost: + bias, tanh, fp32 NCHW image
                 u = empty(N, H2, W2, cpad)
                 bpad = None
@@ -398,7 +437,7 @@ class DiscriminatorEngine(ParamIndex):
         convs = [(i, m) for i, m in enumerate(seq) if isinstance(m, torch.nn.Conv2d)]
         stages = []
         for idx, (i, conv) in enumerate(convs):
-            bn = seq[i + 1] if i + 1 < len(seq) and isinstance(seq[i + 1], torch.nn.BatchNorm2d) else None
+            bn = seq[i + 1] if i + 1 < len(seq) and isinstance(seq[i + 1], (torch.nn.BatchNorm2d, torch.nn.InstanceNorm2d)) else None
             stages.append((i, conv, bn))
         return stages
 
@@ -417,6 +456,14 @@ class DiscriminatorEngine(ParamIndex):
         def empty(*shape, dtype=tdt):
             return torch.empty(shape, dtype=dtype, device=dev)
 
+        # InstanceNorm needs planes of more than one element (16 x 16 through three layers ends at 1 x 1): refused before any launch
+        ch, cw = H, W
+        for (i, conv, bn) in stages[:-1]:
+            ch = ops.conv_out_size(ch, conv.kernel_size[0], conv.stride[0], conv.padding[0])
+            cw = ops.conv_out_size(cw, conv.kernel_size[0], conv.stride[0], conv.padding[0])
+            if is_instance_norm(bn) and ch * cw < 2:
+                raise ValueError(f"Expected more than 1 spatial element when training, got input size "
+                                 f"{[N, conv.out_channels, ch, cw]} (InstanceNorm2d model.{i + 1})")
         recs = []
         nbt_pending = []
         # stage 0: direct conv + bias + LeakyReLU (no norm)
@@ -430,18 +477,28 @@ class DiscriminatorEngine(ParamIndex):
         cur, ch, cw, cc = z, h, w, conv0.out_channels
         for (i, conv, bn) in stages[1:-1]:
             k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-            if conv.bias is not None or bn is None:
-                raise NotImplementedError("PatchGAN middle convs are expected as conv(no bias) -> BatchNorm -> LeakyReLU")
+            inorm = is_instance_norm(bn)
+            if bn is None or (conv.bias is not None and not inorm):
+                raise NotImplementedError("PatchGAN middle convs are expected as conv(no bias) -> BatchNorm -> LeakyReLU or "
+                                          "conv -> InstanceNorm -> LeakyReLU")
             wf, wd = self.packs.get(("conv", i), _ver(conv.weight), lambda conv=conv: self._pack(conv.weight))
             g = cached_geom(ops.geom_conv, N, ch, cw, cc, conv.out_channels, k, s, p)
             oh, ow = g.OH, g.OW
             y = empty(N, oh, ow, conv.out_channels)
+            z = empty(N, oh, ow, conv.out_channels)
+            if inorm:
+                ops.conv_igemm(g, cur, wf, y, None, None)            # the conv's bias cancels in the norm: not added
+                mi = instance_stats(y, bn)
+                ops.in_act_apply(y, mi[0], mi[1], ACT_LEAKY02, z, conv.out_channels, 0)
+                recs.append(dict(kind="mid", conv=conv, bn=bn, inp=cur, y=y, coef=None, stats=True, inorm=mi, geom=g, wd=wd,
+                                 k=k, s=s, p=p, ih=ch, iw=cw, cin=cc, name=f"model.{i}", bnname=f"model.{i + 1}"))
+                cur, ch, cw, cc = z, oh, ow, conv.out_channels
+                continue
             mt = ops.conv_igemm_mtiles(g)
             use_stats = training or bn.running_mean is None
             part = empty(ops.bn_partials_numel(mt, conv.out_channels), dtype=torch.float32) if use_stats else None
             ops.conv_igemm(g, cur, wf, y, None, part)
             coef, stats = bn_coeffs(bn, part, mt, conv.out_channels, N * oh * ow, training, dev, nbt_pending)
-            z = empty(N, oh, ow, conv.out_channels)
             ops.bn_act_apply(y, coef[0], coef[1], ACT_LEAKY02, z, conv.out_channels, 0)
             recs.append(dict(kind="mid", conv=conv, bn=bn, inp=cur, y=y, coef=coef, stats=stats, geom=g, wd=wd,
                              k=k, s=s, p=p, ih=ch, iw=cw, cin=cc, name=f"model.{i}", bnname=f"model.{i + 1}"))
@@ -462,6 +519,25 @@ class DiscriminatorEngine(ParamIndex):
         wd = torch.empty((kh * kw, cin, cout), dtype=self.tdt, device=w.device)
         ops.pack_weight(w.detach().contiguous(), wf, wd, False)
         return wf, wd
+
+    @staticmethod
+    def _mid_conv_bwd(rec, dy, grads, inv_s, empty):
+        """weight gradient (emitted) and data gradient (returned) of a middle conv from dy: the launches of backward() below"""
+        conv = rec["conv"]
+        N, _, _, cout = dy.shape
+        k, s, p, cin = rec["k"], rec["s"], rec["p"], rec["cin"]
+        dw = torch.empty_like(conv.weight, memory_format=torch.contiguous_format)
+        wsl = empty(ops.conv_wgrad_ws_floats(rec["geom"]), dtype=torch.float32)
+        ops.conv_wgrad_det(rec["geom"], rec["inp"], dy, wsl, dw, cout, cin, k * k, inv_s)
+        grads[rec["name"] + ".weight"] = dw
+        dz = empty(N, rec["ih"], rec["iw"], cin)
+        if s == 1:
+            ops.conv_igemm(cached_geom(ops.geom_conv_dgrad_s1, N, rec["ih"], rec["iw"], cin, cout, k, p), dy, rec["wd"], dz)
+        else:
+            gds = [cached_geom(ops.geom_conv_s2_dgrad_class, N, rec["ih"], rec["iw"], cin, cout, k, p, cls >> 1, cls & 1)
+                   for cls in range(4)]
+            ops.conv_igemm_batch(gds, dy, [rec["wd"]] * 4, dz)
+        return dz
 
     def backward(self, ctx, dlogits, need_dx):
         tdt = self.tdt
@@ -491,6 +567,15 @@ class DiscriminatorEngine(ParamIndex):
             conv, coef = rec["conv"], rec["coef"]
             y = rec["y"]
             _, oh, ow, cout = y.shape
+            inorm = rec.get("inorm")
+            if inorm is not None:
+                dy = empty(N, oh, ow, cout)
+                ops.in_act_bwd(y, inorm[0], inorm[1], dz, cout, 0, ACT_LEAKY02, dy, empty(2, N, cout, dtype=torch.float32),
+                               ops.in_workspace(N, oh, ow, cout, dev))
+                dz = self._mid_conv_bwd(rec, dy, grads, inv_s, empty)
+                if conv.bias is not None:                            # cancelled by the norm: exact zeros
+                    grads[rec["name"] + ".bias"] = torch.zeros_like(conv.bias)
+                continue
             nt = ops.bn_bwd_tiles_used(N, oh, ow, False)
             part = empty(ops.bn_partials_numel(ops.bn_bwd_tiles(N, oh, ow), cout), dtype=torch.float32)
             ops.bn_act_bwd_reduce(y, dz, cout, 0, None, coef[0], coef[1], coef[2], coef[3], ACT_LEAKY02, part)

@@ -981,6 +981,52 @@ def colsum(t, pix_stride, coff, N, H, W, y0, x0, h, w, C, gscale, ws, out):
               dt_code(t), _stream())
 
 
+# ---------------------------------------------------------------------------- InstanceNorm (csrc/instnorm.hip)
+def in_ws_numel(N, H, W, C) -> int:
+    """fp32 elements of the workspace gs_in_stats / gs_in_act_bwd need for this shape (0: none)"""
+    return int(_lib.load().gs_in_ws_floats(N, H, W, C))
+
+
+def in_workspace(N, H, W, C, dev):
+    n = in_ws_numel(N, H, W, C)
+    return torch.empty(n, dtype=torch.float32, device=dev) if n else None
+
+
+def in_stats(y, eps, mean, invstd, ws=None):
+    """per (sample, channel) mean and 1 / sqrt(biased variance + eps) of y [N,H,W,C] -> fp32 [N,C] each"""
+    N, H, W, C = y.shape
+    if not y.is_contiguous():
+        raise ValueError("in_stats: y must be dense NHWC")
+    _f32(mean, "mean"); _f32(invstd, "invstd"); _f32(ws, "ws")
+    if mean.numel() != N * C or invstd.numel() != N * C or (ws.numel() if ws is not None else 0) < in_ws_numel(N, H, W, C):
+        raise ValueError("in_stats: mean / invstd must hold N*C floats and ws in_ws_numel(N, H, W, C)")
+    _lib.call("gs_in_stats", _p(y), float(eps), _p(mean), _p(invstd), _p(ws), N, H, W, C, dt_code(y), _stream())
+
+
+def in_act_apply(y, mean, invstd, act, z, z_stride, z_coff, keep_mask=None, keep_scale=1.0, z2=None, act2=ACT_NONE,
+                 z2_stride=0, z2_coff=0):
+    N, H, W, C = y.shape
+    if not y.is_contiguous():
+        raise ValueError("in_act_apply: y must be dense NHWC")
+    _f32(mean, "mean"); _f32(invstd, "invstd")
+    if z.dtype != y.dtype or (z2 is not None and z2.dtype != y.dtype):
+        raise TypeError("in_act_apply: y, z and z2 must share one 16-bit dtype")
+    _lib.call("gs_in_act_apply", _p(y), _p(mean), _p(invstd), act, _p(z), z_stride, z_coff, _p(keep_mask), float(keep_scale),
+              _p(z2), act2, z2_stride, z2_coff, N, H, W, C, dt_code(y), _stream())
+
+
+def in_act_bwd(y, mean, invstd, dz_a, sa, ca, act, dy, gmeans, ws=None, dz_b=None, act_b=ACT_NONE, keep_mask=None, keep_scale=1.0):
+    """dy of act(instance_norm(y)) [two consumers / dropout]; gmeans fp32 [2,N,C] receives mean_plane(g), mean_plane(g * xh)"""
+    N, H, W, C = y.shape
+    _f32(mean, "mean"); _f32(invstd, "invstd"); _f32(gmeans, "gmeans"); _f32(ws, "ws")
+    if gmeans.numel() != 2 * N * C or (ws.numel() if ws is not None else 0) < in_ws_numel(N, H, W, C):
+        raise ValueError("in_act_bwd: gmeans must hold 2*N*C floats and ws in_ws_numel(N, H, W, C)")
+    if dz_a.dtype != y.dtype or dy.dtype != y.dtype or (dz_b is not None and dz_b.dtype != y.dtype):
+        raise TypeError("in_act_bwd: y, dz_a, dz_b and dy must share one 16-bit dtype")
+    _lib.call("gs_in_act_bwd", _p(y), _p(mean), _p(invstd), _p(dz_a), sa, ca, act, _p(keep_mask), float(keep_scale), _p(dz_b), act_b,
+              _p(dy), _p(gmeans), _p(ws), N, H, W, C, dt_code(y), _stream())
+
+
 # ---------------------------------------------------------------------------- packing / layout
 def pack_weight(w, w_fwd, w_dgrad, transposed: bool):
     _dev(w)
