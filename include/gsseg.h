@@ -804,6 +804,54 @@ int gs_in_act_bwd(const void* y, const float* mean, const float* invstd, const v
                   const uint8_t* keep_mask, float keep_scale, const void* dz_b, int act_b, void* dy, float* gmeans, float* ws,
                   int N, int H, int W, int C, int dtype, void* stream);
 
+/* ReflectionPad2d around the convolutions of the ResNet generator (reference models_pix2pix/networks.py:321-439, `--netG
+ * resnet_9blocks` / `resnet_6blocks`; csrc/reflect.hip).  ReflectionPad2d excludes the edge: padded index -1 is pixel 1, index H is
+ * pixel H-2.  Tensors are dense NHWC 16-bit; a tensor "padded by p" is dense [N, H+2p, W+2p, C].
+ * Every entry point: GS_EINVAL before any launch for a bad dtype, a null or misaligned pointer (16 bytes; keep masks 8; fp32 images
+ * and the tanh pair 4), C %% 8 != 0, pad outside 0..8, H <= pad or W <= pad (torch: "Padding size should be less than the
+ * corresponding input dimension").  No allocation, no synchronisation, no atomics; every sum has one fixed order.
+ * gs_reflect_norm_apply: z = [res +] act(norm(y)) [* keep_mask * keep_scale], written into the tensor padded by `pad`, interior and
+ *   reflected border in one pass (pad 0: dense).  norm 0: identity (coef_a = coef_b = NULL); 1: y * coef_a[c] + coef_b[c] (BatchNorm
+ *   scale / shift from gs_bn_finalize / gs_bn_eval_coeffs); 2: (y - coef_a[n][c]) * coef_b[n][c] (InstanceNorm mean / invstd from
+ *   gs_in_stats).  act: none or ReLU.  res (may be NULL): the interior of a tensor padded by res_pad, read at the same pixel -- the
+ *   residual stream of a ResnetBlock lives in the padded input of its first conv.  keep_mask uint8 [N,H,W,C] (may be NULL).
+ * gs_reflect_fold_add: backward of the pad.  out [N,H,W,C] = fold(dpad) [+ add]: each border element of dpad (the gradient w.r.t.
+ *   the padded tensor, from the data gradient of the pad-0 conv) is added to the pixel it mirrors; add (dense, may be NULL) is the
+ *   residual stream's gradient.  fp32 sums in the order rows (own, low mirror, high mirror) x columns (same), then add; one rounding.
+ * gs_reflect_pad_image / gs_reflect_fold_image: the same pad and fold for fp32 NCHW images (first 7x7 conv and its data gradient).
+ * gs_tanh_fwd: t = tanh(x) (may be in place); gs_tanh_bwd: d = gscale * dout * (1 - t) * (1 + t) (d may alias dout); fp32, n elements. */
+int gs_reflect_norm_apply(const void* y, const float* coef_a, const float* coef_b, int norm, int act, const void* res, int res_pad,
+                          const uint8_t* keep_mask, float keep_scale, void* z, int pad, int N, int H, int W, int C, int dtype,
+                          void* stream);
+int gs_reflect_fold_add(const void* dpad, const void* add, void* out, int pad, int N, int H, int W, int C, int dtype, void* stream);
+int gs_reflect_pad_image(const float* x, float* xp, int pad, int N, int C, int H, int W, void* stream);
+int gs_reflect_fold_image(const float* dxp, float* dx, int pad, int N, int C, int H, int W, void* stream);
+int gs_tanh_fwd(const float* x, float* t, int64_t n, void* stream);
+int gs_tanh_bwd(const float* t, const float* dout, float gscale, float* d, int64_t n, void* stream);
+
+/* The two 7x7 ends of the ResNet generator (csrc/ends.hip): k x k, stride-1 convolutions between an fp32 NCHW image of Cimg = 1..4
+ * channels and a dense 16-bit NHWC tensor of C16 channels, C16 ANY multiple of 8 (the weights are tiled through LDS, 32 channels of
+ * the wide side at a time; gs_conv_smallcin_* / gs_conv_smallcout_* hold the whole tensor, at most 8192 floats).  k <= 7, 0 <= pad < k;
+ * output plane = input plane + 2 pad - k + 1, zeros outside the input.  w is the module's fp32 weight: w_img_major 0: [C16][Cimg][k][k]
+ * (the stem), 1: [Cimg][C16][k][k] (the head); flip 1 reads the taps reversed (k*k - 1 - t): with pad = k - 1 that is the data
+ * gradient of the pad-0 convolution, back onto the padded grid.  GS_EINVAL before any launch for a bad dtype, a null or misaligned
+ * pointer (16 bytes for 16-bit tensors, 4 for fp32), C16 %% 8 != 0, Cimg outside 1..4, or planes that do not match.  No atomics.
+ * gs_conv_ends_to_c16: out [N,OH,OW,C16] from img [N,Cimg,IH,IW]; bn_partials (may be NULL): [gs_conv_ends_mtiles][2][C16] sums and
+ *   sums of squares of the unrounded outputs, as the other conv epilogues write them.  Stem forward / head data gradient.
+ * gs_conv_ends_to_img: out [N,Cimg,OH,OW] = gscale * conv(t16 [N,IH,IW,C16]) + bias (may be NULL).  Head forward / stem data gradient.
+ * gs_conv_ends_wgrad: dw[.] = gscale * sum over the pixels p of t16 [N,TH,TW,C16] and the taps of t16[p][c16] * img[cimg][p + tap - pad],
+ *   img [N,Cimg,BH,BW] with BH = TH + k - 1 - 2 pad, written in w's layout (flip as above); db (may be NULL) [Cimg] = gscale * sum img.
+ *   pad 0, flip 0: the stem's weight gradient (t16 = dy, img = the padded input); pad k-1, flip 1: the head's (t16 = the padded
+ *   input, img = the gradient of the head's output).  ws: gs_conv_ends_wgrad_ws_floats floats; block slabs summed in block order. */
+int gs_conv_ends_mtiles(int N, int OH, int OW);
+int gs_conv_ends_to_c16(const float* img, const float* w, void* out, float* bn_partials, int N, int Cimg, int IH, int IW, int C16,
+                        int OH, int OW, int k, int pad, int flip, int w_img_major, int dtype, void* stream);
+int gs_conv_ends_to_img(const void* t16, const float* w, const float* bias, float* out, int N, int IH, int IW, int C16, int Cimg,
+                        int OH, int OW, int k, int pad, int flip, int w_img_major, float gscale, int dtype, void* stream);
+int64_t gs_conv_ends_wgrad_ws_floats(int N, int TH, int TW, int Cimg, int C16, int k);
+int gs_conv_ends_wgrad(const void* t16, const float* img, float* dw, float* db, float* ws, int N, int TH, int TW, int C16, int Cimg,
+                       int BH, int BW, int k, int pad, int flip, int w_img_major, float gscale, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,17 @@ PROTOTYPES = {
     "gs_in_stats": (c_int, [_P, c_float, _F, _F, _F] + [c_int] * 5 + [c_void_p]),
     "gs_in_act_apply": (c_int, [_P, _F, _F, c_int, _P, c_int, c_int, _P, c_float, _P, c_int, c_int, c_int] + [c_int] * 5 + [c_void_p]),
     "gs_in_act_bwd": (c_int, [_P, _F, _F, _P, c_int, c_int, c_int, _P, c_float, _P, c_int, _P, _F, _F] + [c_int] * 5 + [c_void_p]),
+    "gs_reflect_norm_apply": (c_int, [_P, _F, _F, c_int, c_int, _P, c_int, _P, c_float, _P] + [c_int] * 6 + [c_void_p]),
+    "gs_reflect_fold_add": (c_int, [_P, _P, _P] + [c_int] * 6 + [c_void_p]),
+    "gs_reflect_pad_image": (c_int, [_F, _F] + [c_int] * 5 + [c_void_p]),
+    "gs_reflect_fold_image": (c_int, [_F, _F] + [c_int] * 5 + [c_void_p]),
+    "gs_tanh_fwd": (c_int, [_F, _F, c_int64, c_void_p]),
+    "gs_tanh_bwd": (c_int, [_F, _F, c_float, _F, c_int64, c_void_p]),
+    "gs_conv_ends_mtiles": (c_int, [c_int] * 3),
+    "gs_conv_ends_to_c16": (c_int, [_F, _F, _P, _F] + [c_int] * 12 + [c_void_p]),
+    "gs_conv_ends_to_img": (c_int, [_P, _F, _F, _F] + [c_int] * 11 + [c_float, c_int, c_void_p]),
+    "gs_conv_ends_wgrad_ws_floats": (c_int64, [c_int] * 6),
+    "gs_conv_ends_wgrad": (c_int, [_P, _F, _F, _F, _F] + [c_int] * 11 + [c_float, c_int, c_void_p]),
 }
 
 _lib = None

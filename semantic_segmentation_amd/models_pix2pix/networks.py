@@ -2,7 +2,7 @@
 
 Same public names, module tree and state-dict keys as the reference for the parts reached by
 `--model pix2pix` defaults: `UnetGenerator` (+ `UnetSkipConnectionBlock`, `Cell_upconv`, `MixedOp_upconv`),
-`NLayerDiscriminator`, `GANLoss`, `get_norm_layer`, `init_weights`, `init_net`, `define_G`, `define_D`, and the
+`ResnetGenerator` (+ `ResnetBlock`), `NLayerDiscriminator`, `GANLoss`, `get_norm_layer`, `init_weights`, `init_net`, `define_G`, `define_D`, and the
 architecture tensors `upconv_arch` / `conv_arch` / `arch_parameters()` (module globals, :443,:477-484).
 The leaf torch modules only hold parameters; `UnetGenerator.forward` and `NLayerDiscriminator.forward`
 run whole-network plans on the HIP kernels (pix2pix_engine.py).  No ATen / CPU fallback."""
@@ -75,6 +75,10 @@ def define_G(input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, in
         net = UnetGenerator(input_nc, output_nc, 7, ngf, norm_layer=norm_layer, use_dropout=use_dropout)
     elif netG == 'unet_256':
         net = UnetGenerator(input_nc, output_nc, 8, ngf, norm_layer=norm_layer, use_dropout=use_dropout)
+    elif netG == 'resnet_9blocks':
+        net = ResnetGenerator(input_nc, output_nc, ngf, norm_layer=norm_layer, use_dropout=use_dropout, n_blocks=9)
+    elif netG == 'resnet_6blocks':
+        net = ResnetGenerator(input_nc, output_nc, ngf, norm_layer=norm_layer, use_dropout=use_dropout, n_blocks=6)
     else:
         raise NotImplementedError('Generator model name [%s] is not on the MI355X hot path' % netG)
     return init_net(net, init_type, init_gain, gpu_ids)
@@ -248,6 +252,69 @@ class UnetGenerator(nn.Module):
     def forward(self, input, dropout_masks=None):
         """`dropout_masks`: optional list of uint8 keep-masks (NHWC) for the dropout blocks, innermost first;
         default draws them with torch.rand on the device (train mode) -- not the ATen Philox stream."""
+        return self._engine.run(input, dropout_masks)
+
+
+class ResnetBlock(nn.Module):
+    """networks.py:382-439: same Sequential layout (ReflectionPad2d, Conv2d, norm, ReLU, [Dropout], ReflectionPad2d, Conv2d, norm)
+    -- convs at conv_block.1 and .5 (.6 with dropout)."""
+
+    def __init__(self, dim, padding_type, norm_layer, use_dropout, use_bias):
+        super(ResnetBlock, self).__init__()
+        self.conv_block = self.build_conv_block(dim, padding_type, norm_layer, use_dropout, use_bias)
+
+    def build_conv_block(self, dim, padding_type, norm_layer, use_dropout, use_bias):
+        if padding_type != 'reflect':
+            raise NotImplementedError("ResnetBlock padding [%s] is not on the MI355X hot path: 'reflect' is supported" % padding_type)
+        conv_block = [nn.ReflectionPad2d(1), nn.Conv2d(dim, dim, kernel_size=3, padding=0, bias=use_bias), norm_layer(dim),
+                      nn.ReLU(True)]
+        if use_dropout:
+            conv_block += [nn.Dropout(0.5)]
+        conv_block += [nn.ReflectionPad2d(1), nn.Conv2d(dim, dim, kernel_size=3, padding=0, bias=use_bias), norm_layer(dim)]
+        return nn.Sequential(*conv_block)
+
+    def forward(self, x):
+        raise RuntimeError("ResnetBlock runs inside ResnetGenerator.forward (HIP engine)")
+
+
+class ResnetGenerator(nn.Module):
+    """networks.py:321-379 (the generator of `--netG resnet_9blocks`, the default of options/base_options.py:34, and
+    `resnet_6blocks`): same Sequential indices, hence the same state-dict keys."""
+
+    def __init__(self, input_nc, output_nc, ngf=64, norm_layer=nn.BatchNorm2d, use_dropout=False, n_blocks=6,
+                 padding_type='reflect', compute_dtype=None):
+        assert (n_blocks >= 0)
+        super(ResnetGenerator, self).__init__()
+        from .resnet_engine import ResnetGeneratorEngine, check_supported
+        use_bias = check_supported(input_nc, output_nc, ngf, norm_layer, padding_type)
+        model = [nn.ReflectionPad2d(3), nn.Conv2d(input_nc, ngf, kernel_size=7, padding=0, bias=use_bias), norm_layer(ngf),
+                 nn.ReLU(True)]
+        n_downsampling = 2
+        for i in range(n_downsampling):
+            mult = 2 ** i
+            model += [nn.Conv2d(ngf * mult, ngf * mult * 2, kernel_size=3, stride=2, padding=1, bias=use_bias),
+                      norm_layer(ngf * mult * 2), nn.ReLU(True)]
+        mult = 2 ** n_downsampling
+        for i in range(n_blocks):
+            model += [ResnetBlock(ngf * mult, padding_type=padding_type, norm_layer=norm_layer, use_dropout=use_dropout,
+                                  use_bias=use_bias)]
+        for i in range(n_downsampling):
+            mult = 2 ** (n_downsampling - i)
+            model += [nn.ConvTranspose2d(ngf * mult, int(ngf * mult / 2), kernel_size=3, stride=2, padding=1, output_padding=1,
+                                         bias=use_bias), norm_layer(int(ngf * mult / 2)), nn.ReLU(True)]
+        model += [nn.ReflectionPad2d(3)]
+        model += [nn.Conv2d(ngf, output_nc, kernel_size=7, padding=0)]
+        model += [nn.Tanh()]
+        self.model = nn.Sequential(*model)
+        object.__setattr__(self, "_engine", ResnetGeneratorEngine(self, compute_dtype))
+
+    @property
+    def engine(self):
+        return self._engine
+
+    def forward(self, input, dropout_masks=None):
+        """`dropout_masks`: optional list of uint8 keep-masks (NHWC [N,H/4,W/4,4*ngf]) for the blocks' dropout, one per block, first
+        block first; default draws them with torch.rand on the device (train mode) -- not the ATen Philox stream."""
         return self._engine.run(input, dropout_masks)
 
 

@@ -1027,6 +1027,149 @@ def in_act_bwd(y, mean, invstd, dz_a, sa, ca, act, dy, gmeans, ws=None, dz_b=Non
               _p(dy), _p(gmeans), _p(ws), N, H, W, C, dt_code(y), _stream())
 
 
+# ---------------------------------------------------------------------------- ReflectionPad2d passes (csrc/reflect.hip)
+NORM_NONE, NORM_BATCH, NORM_INSTANCE = 0, 1, 2
+
+
+def reflect_norm_apply(y, coef_a, coef_b, norm, act, z, pad, res=None, res_pad=0, keep_mask=None, keep_scale=1.0):
+    """z [N,H+2p,W+2p,C] = [res +] act(norm(y)) [* keep * keep_scale], interior and reflected border in one pass (pad 0: dense).
+    norm: NORM_NONE / NORM_BATCH (coef_a / coef_b = scale / shift [C]) / NORM_INSTANCE (mean / invstd [N,C]); res: a tensor padded
+    by res_pad whose interior is added (the residual stream)."""
+    _dev(y)
+    N, H, W, C = y.shape
+    _f32(coef_a, "coef_a"); _f32(coef_b, "coef_b")
+    if not (y.is_contiguous() and z.is_contiguous()) or (res is not None and not res.is_contiguous()):
+        raise ValueError("reflect_norm_apply: y, z and res must be dense NHWC")
+    if z.dtype != y.dtype or (res is not None and res.dtype != y.dtype):
+        raise TypeError("reflect_norm_apply: y, z and res must share one 16-bit dtype")
+    if tuple(z.shape) != (N, H + 2 * pad, W + 2 * pad, C):
+        raise ValueError(f"reflect_norm_apply: z must be [N, H+2*pad, W+2*pad, C], got {tuple(z.shape)}")
+    if res is not None and tuple(res.shape) != (N, H + 2 * res_pad, W + 2 * res_pad, C):
+        raise ValueError(f"reflect_norm_apply: res must be [N, H+2*res_pad, W+2*res_pad, C], got {tuple(res.shape)}")
+    want = {NORM_NONE: 0, NORM_BATCH: C, NORM_INSTANCE: N * C}.get(norm)
+    if want is None or (coef_a.numel() if coef_a is not None else 0) != want or (coef_b.numel() if coef_b is not None else 0) != want:
+        raise ValueError("reflect_norm_apply: coefficients must hold C (batch) / N*C (instance) floats, none without a norm")
+    if keep_mask is not None and (keep_mask.dtype != torch.uint8 or keep_mask.numel() != y.numel() or not keep_mask.is_contiguous()):
+        raise ValueError("reflect_norm_apply: keep_mask must be a dense uint8 [N,H,W,C]")
+    _lib.call("gs_reflect_norm_apply", _p(y), _p(coef_a), _p(coef_b), norm, act, _p(res), res_pad, _p(keep_mask), float(keep_scale),
+              _p(z), pad, N, H, W, C, dt_code(y), _stream())
+
+
+def reflect_fold_add(dpad, out, pad, add=None):
+    """out [N,H,W,C] = fold(dpad [N,H+2p,W+2p,C]) [+ add]: the backward of a reflection pad, fused with the residual stream's
+    gradient; fixed summation order."""
+    _dev(dpad)
+    N, H, W, C = out.shape
+    if tuple(dpad.shape) != (N, H + 2 * pad, W + 2 * pad, C) or (add is not None and add.shape != out.shape):
+        raise ValueError("reflect_fold_add: dpad must be [N, H+2*pad, W+2*pad, C] and add like out")
+    if not (dpad.is_contiguous() and out.is_contiguous()) or (add is not None and not add.is_contiguous()):
+        raise ValueError("reflect_fold_add: dense NHWC tensors")
+    if dpad.dtype != out.dtype or (add is not None and add.dtype != out.dtype):
+        raise TypeError("reflect_fold_add: dpad, add and out must share one 16-bit dtype")
+    _lib.call("gs_reflect_fold_add", _p(dpad), _p(add), _p(out), pad, N, H, W, C, dt_code(out), _stream())
+
+
+def reflect_pad_image(x, xp, pad):
+    """xp fp32 [N,C,H+2p,W+2p] = ReflectionPad2d(pad)(x fp32 NCHW)"""
+    _dev(x)
+    _f32(x, "x"); _f32(xp, "xp")
+    N, C, H, W = x.shape
+    if tuple(xp.shape) != (N, C, H + 2 * pad, W + 2 * pad):
+        raise ValueError("reflect_pad_image: xp must be [N, C, H+2*pad, W+2*pad]")
+    _lib.call("gs_reflect_pad_image", _p(x), _p(xp), pad, N, C, H, W, _stream())
+
+
+def reflect_fold_image(dxp, dx, pad):
+    """dx fp32 [N,C,H,W] = fold(dxp fp32 [N,C,H+2p,W+2p]): backward of reflect_pad_image"""
+    _dev(dxp)
+    _f32(dxp, "dxp"); _f32(dx, "dx")
+    N, C, H, W = dx.shape
+    if tuple(dxp.shape) != (N, C, H + 2 * pad, W + 2 * pad):
+        raise ValueError("reflect_fold_image: dxp must be [N, C, H+2*pad, W+2*pad]")
+    _lib.call("gs_reflect_fold_image", _p(dxp), _p(dx), pad, N, C, H, W, _stream())
+
+
+def tanh_fwd(x, t):
+    _dev(x)
+    _f32(x, "x"); _f32(t, "t")
+    if t.numel() != x.numel():
+        raise ValueError("tanh_fwd: sizes differ")
+    _lib.call("gs_tanh_fwd", _p(x), _p(t), x.numel(), _stream())
+
+
+def tanh_bwd(t, dout, gscale, d):
+    """d = gscale * dout * (1 - t) * (1 + t)"""
+    _dev(t)
+    _f32(t, "t"); _f32(dout, "dout"); _f32(d, "d")
+    if dout.numel() != t.numel() or d.numel() != t.numel():
+        raise ValueError("tanh_bwd: sizes differ")
+    _lib.call("gs_tanh_bwd", _p(t), _p(dout), float(gscale), _p(d), t.numel(), _stream())
+
+
+# ---------------------------------------------------------------------------- the 7x7 ends (csrc/ends.hip)
+def _ends_w(w, w_img_major, cimg, c16, k, who):
+    _f32(w, "w")
+    want = (cimg, c16, k, k) if w_img_major else (c16, cimg, k, k)
+    if tuple(w.shape) != want or not w.is_contiguous():
+        raise ValueError(f"{who}: weight must be a dense {want}, got {tuple(w.shape)}")
+
+
+def conv_ends_mtiles(N, OH, OW) -> int:
+    return _lib.load().gs_conv_ends_mtiles(N, OH, OW)
+
+
+def conv_ends_to_c16(img, w, out, bn_partials, pad=0, flip=False, w_img_major=False):
+    """out 16-bit [N,OH,OW,C16] = conv(img fp32 [N,Cimg,IH,IW]), k x k stride 1, OH = IH + 2 pad - k + 1; any C16 % 8 == 0.
+    (pad 0, stem weight): the stem forward, with BatchNorm partials; (pad k-1, flip, head weight): the head's data gradient."""
+    _dev(img)
+    _f32(img, "img"); _f32(bn_partials, "bn_partials")
+    N, Cimg, IH, IW = img.shape
+    _, OH, OW, C16 = out.shape
+    k = w.shape[-1]
+    _ends_w(w, w_img_major, Cimg, C16, k, "conv_ends_to_c16")
+    if not (img.is_contiguous() and out.is_contiguous()) or out.shape[0] != N:
+        raise ValueError("conv_ends_to_c16: dense img [N,Cimg,IH,IW] and out [N,OH,OW,C16]")
+    _lib.call("gs_conv_ends_to_c16", _p(img), _p(w), _p(out), _p(bn_partials), N, Cimg, IH, IW, C16, OH, OW, k, pad, int(flip),
+              int(w_img_major), dt_code(out), _stream())
+
+
+def conv_ends_to_img(t16, w, bias, out, pad=0, flip=False, w_img_major=True, gscale=1.0):
+    """out fp32 [N,Cimg,OH,OW] = gscale * conv(t16 [N,IH,IW,C16]) + bias.  (pad 0, head weight): the head forward;
+    (pad k-1, flip, stem weight): the stem's data gradient."""
+    _dev(t16)
+    _f32(out, "out"); _f32(bias, "bias")
+    N, IH, IW, C16 = t16.shape
+    _, Cimg, OH, OW = out.shape
+    k = w.shape[-1]
+    _ends_w(w, w_img_major, Cimg, C16, k, "conv_ends_to_img")
+    if not (t16.is_contiguous() and out.is_contiguous()) or out.shape[0] != N or (bias is not None and bias.numel() != Cimg):
+        raise ValueError("conv_ends_to_img: dense t16 [N,IH,IW,C16], out [N,Cimg,OH,OW], bias [Cimg]")
+    _lib.call("gs_conv_ends_to_img", _p(t16), _p(w), _p(bias), _p(out), N, IH, IW, C16, Cimg, OH, OW, k, pad, int(flip),
+              int(w_img_major), float(gscale), dt_code(t16), _stream())
+
+
+def conv_ends_wgrad(t16, img, dw, db, pad=0, flip=False, w_img_major=False, gscale=1.0):
+    """dw (in the weight's own layout) = gscale * sum_p t16[p][c16] * img[cimg][p + tap - pad]; db [Cimg] = gscale * sum img.
+    (t16 = dy, img = padded input, pad 0): the stem; (t16 = padded input, img = d out, pad k-1, flip, head weight): the head."""
+    _dev(t16)
+    _f32(img, "img"); _f32(dw, "dw"); _f32(db, "db")
+    N, TH, TW, C16 = t16.shape
+    _, Cimg, BH, BW = img.shape
+    k = dw.shape[-1]
+    _ends_w(dw, w_img_major, Cimg, C16, k, "conv_ends_wgrad")
+    if not (t16.is_contiguous() and img.is_contiguous()) or img.shape[0] != N or (db is not None and db.numel() != Cimg):
+        raise ValueError("conv_ends_wgrad: dense t16 [N,TH,TW,C16], img [N,Cimg,BH,BW], db [Cimg]")
+    ws = torch.empty(int(_lib.load().gs_conv_ends_wgrad_ws_floats(N, TH, TW, Cimg, C16, k)), dtype=torch.float32, device=t16.device)
+    _lib.call("gs_conv_ends_wgrad", _p(t16), _p(img), _p(dw), _p(db), _p(ws), N, TH, TW, C16, Cimg, BH, BW, k, pad, int(flip),
+              int(w_img_major), float(gscale), dt_code(t16), _stream())
+
+
+def geom_convT3_class(N, IH, IW, Cin, Cout, py, px, **kw) -> GsConvGeom:
+    """Sub-pixel class (py,px) of ConvTranspose2d(3, stride 2, padding 1, output_padding 1): 1 / 2 / 2 / 4 taps, output 2IH x 2IW
+    (the extra row / column of output_padding is the trailing one); weight slots index the [9][Cout][Cin] pack."""
+    return geom_convT_class(N, IH, IW, Cin, Cout, 3, 1, py, px, OH=2 * IH, OW=2 * IW, **kw)
+
+
 # ---------------------------------------------------------------------------- packing / layout
 def pack_weight(w, w_fwd, w_dgrad, transposed: bool):
     _dev(w)
