@@ -852,6 +852,26 @@ int64_t gs_conv_ends_wgrad_ws_floats(int N, int TH, int TW, int Cimg, int C16, i
 int gs_conv_ends_wgrad(const void* t16, const float* img, float* dw, float* db, float* ws, int N, int TH, int TW, int C16, int Cimg,
                        int BH, int BW, int k, int pad, int flip, int w_img_major, float gscale, int dtype, void* stream);
 
+/* The image-side conv of the Pix2Pix networks for Cin = 5..16 image channels (csrc/ends_wide.hip): the PatchGAN's model.0
+ * (models_pix2pix/networks.py:640), the U-Net generator's outermost down-conv (:582) -- both k 4 / stride 2 / pad 1 -- and
+ * PixelDiscriminator.net.0 (:686, k 1 / stride 1 / pad 0), between an fp32 NCHW image [N,Cin,IH,IW] and a dense 16-bit NHWC tensor
+ * [N,OH,OW,Cout], Cout any multiple of 8 up to 128; w is the module's fp32 weight [Cout][Cin][k][k].  The image is not rounded to 16
+ * bits; products are fp32 x fp32 accumulated in fp32 (v_mfma_f32_32x32x2_f32 in the forward and the weight gradient).
+ * Checked before any launch: GS_EINVAL for a null or misaligned pointer (16 bytes for the 16-bit tensor, 4 for fp32), a bad dtype or
+ * planes that do not match; GS_EUNSUPPORTED for Cin outside 5..16, Cout not a multiple of 8 or above 128, or another (k, stride, pad).
+ * gs_conv_imgwide_fwd  : y = act(conv(x, w) + bias); bias may be NULL; act GS_ACT_NONE or GS_ACT_LEAKY02 (else GS_EUNSUPPORTED).
+ * gs_conv_imgwide_wgrad: dw [Cout][Cin][k][k] = gscale * sum over pixels of dy * x (overwrites).  ws: gs_conv_imgwide_wgrad_ws_floats
+ *   floats of per-block partial slabs, added in slab order by a second launch: no atomics, two runs give equal bits.  (The bias
+ *   gradient of these layers is gs_colsum over dy.)
+ * gs_conv_imgwide_dgrad: dx fp32 NCHW [N,Cin,IH,IW] = gscale * conv_transpose(dy, w) (overwrites every element). */
+int gs_conv_imgwide_fwd(const float* x, const float* w, const float* bias, void* y, int N, int Cin, int IH, int IW, int Cout, int OH,
+                        int OW, int k, int stride, int pad, int act, int dtype, void* stream);
+int64_t gs_conv_imgwide_wgrad_ws_floats(int N, int OH, int OW, int Cin, int Cout, int k);
+int gs_conv_imgwide_wgrad(const float* x, const void* dy, float* dw, float* ws, int N, int Cin, int IH, int IW, int Cout, int OH,
+                          int OW, int k, int stride, int pad, float gscale, int dtype, void* stream);
+int gs_conv_imgwide_dgrad(const void* dy, const float* w, float* dx, int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int k,
+                          int stride, int pad, float gscale, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

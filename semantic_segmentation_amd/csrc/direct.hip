@@ -931,6 +931,14 @@ __device__ __forceinline__ void head_bn_act(const HArgs& a, const float* sc, con
     }
 }
 
+// lanes that share a pixel of the small-Cout forward: the largest power of two up to min(nch, 64) 8-channel chunks (nch itself
+// when it is a power of two; 384 channels: 32 lanes, half of which take a second chunk)
+__host__ __device__ __forceinline__ int head_group_lanes(int nch) {
+    int gl = 1;
+    while (2 * gl <= nch && gl < 64) gl *= 2;
+    return gl;
+}
+
 // wl layout [c][tap][Cin]
 __device__ __forceinline__ void load_head_weights(const HArgs& a, float* wl) {
     const int kk = a.k * a.k;
@@ -949,7 +957,7 @@ __global__ __launch_bounds__(256) void smallcout_fwd_kernel(const HArgs a) {
     __syncthreads();
     const int kk = a.k * a.k;
     const int nch = a.Cin >> 3;
-    const int gl = nch < 64 ? nch : 64;           // lanes cooperating on one pixel (power of two)
+    const int gl = head_group_lanes(nch);         // lanes cooperating on one pixel (power of two)
     const int groups = 256 / gl;
     const int li = threadIdx.x % gl, grp = threadIdx.x / gl;
     const int M = a.N * a.OH * a.OW;                     // host guarantees < 2^31
@@ -1727,7 +1735,7 @@ static int check_head(const char* who, int N, int IH, int IW, int Cin, int Cout,
     GS_CHECK_ARG(N > 0 && IH > 0 && IW > 0 && OH > 0 && OW > 0, "%s: bad dims", who);
     GS_CHECK_ARG(Cout >= 1 && Cout <= 4, "%s: Cout=%d must be 1..4", who, Cout);
     const int nch = Cin / 8;
-    GS_CHECK_ARG(Cin % 8 == 0 && nch >= 1 && (nch & (nch - 1)) == 0 && nch <= 256, "%s: Cin=%d must be 8*2^j <= 2048", who, Cin);
+    GS_CHECK_ARG(Cin % 8 == 0 && nch >= 1 && nch <= 256, "%s: Cin=%d must be a multiple of 8 up to 2048", who, Cin);
     GS_CHECK_ARG(k >= 1 && stride >= 1 && pad >= 0 && Cout * k * k * Cin <= SC_MAX_W, "%s: weights exceed %d floats", who, SC_MAX_W);
     GS_CHECK_ARG(OH == (IH + 2 * pad - k) / stride + 1 && OW == (IW + 2 * pad - k) / stride + 1, "%s: output size mismatch", who);
     GS_CHECK_ARG(dtype == GS_F16 || dtype == GS_BF16, "%s: bad dtype", who);
@@ -1745,7 +1753,7 @@ static int smallcout_fwd_impl(const void* x, const float* w, const float* bias, 
     a.bn_scale = bn_scale; a.bn_shift = bn_shift; a.bn_slope = bn_slope;
     a.x = (const unsigned short*)x; a.w = w; a.bias = bias; a.y = y;
     a.N = N; a.IH = IH; a.IW = IW; a.Cin = Cin; a.Cout = Cout; a.OH = OH; a.OW = OW; a.k = k; a.stride = stride; a.pad = pad;
-    const int nch = Cin / 8, gl = nch < 64 ? nch : 64, groups = 256 / gl;
+    const int nch = Cin / 8, gl = head_group_lanes(nch), groups = 256 / gl;
     int64_t nb = cdiv64((int64_t)N * OH * OW, groups);
     if (nb > 8192) nb = 8192;
     hipStream_t s = (hipStream_t)stream;

@@ -2,7 +2,7 @@
 
 Same public names, module tree and state-dict keys as the reference for the parts reached by
 `--model pix2pix` defaults: `UnetGenerator` (+ `UnetSkipConnectionBlock`, `Cell_upconv`, `MixedOp_upconv`),
-`ResnetGenerator` (+ `ResnetBlock`), `NLayerDiscriminator`, `GANLoss`, `get_norm_layer`, `init_weights`, `init_net`, `define_G`, `define_D`, and the
+`ResnetGenerator` (+ `ResnetBlock`), `NLayerDiscriminator`, `PixelDiscriminator`, `GANLoss`, `get_norm_layer`, `init_weights`, `init_net`, `define_G`, `define_D`, and the
 architecture tensors `upconv_arch` / `conv_arch` / `arch_parameters()` (module globals, :443,:477-484).
 The leaf torch modules only hold parameters; `UnetGenerator.forward` and `NLayerDiscriminator.forward`
 run whole-network plans on the HIP kernels (pix2pix_engine.py).  No ATen / CPU fallback."""
@@ -90,6 +90,8 @@ def define_D(input_nc, ndf, netD, n_layers_D=3, norm='batch', init_type='normal'
         net = NLayerDiscriminator(input_nc, ndf, n_layers=3, norm_layer=norm_layer)
     elif netD == 'n_layers':
         net = NLayerDiscriminator(input_nc, ndf, n_layers_D, norm_layer=norm_layer)
+    elif netD == 'pixel':
+        net = PixelDiscriminator(input_nc, ndf, norm_layer=norm_layer)
     else:
         raise NotImplementedError('Discriminator model name [%s] is not on the MI355X hot path' % netD)
     return init_net(net, init_type, init_gain, gpu_ids)
@@ -338,6 +340,31 @@ class NLayerDiscriminator(nn.Module):
         self.model = nn.Sequential(*sequence)
         from .pix2pix_engine import DiscriminatorEngine
         object.__setattr__(self, "_engine", DiscriminatorEngine(self, compute_dtype))
+
+    @property
+    def engine(self):
+        return self._engine
+
+    def forward(self, input):
+        return self._engine.run(input)
+
+
+class PixelDiscriminator(nn.Module):
+    """networks.py:668-697 1x1 PatchGAN (pixelGAN): the reference's module tree (Sequential `net`: convs at 0, 2, 5; the norm at 3;
+    the last conv carries a bias only under InstanceNorm, :691) on the PatchGAN plan with 1x1 kernels (DiscriminatorEngine)."""
+
+    def __init__(self, input_nc, ndf=64, norm_layer=nn.BatchNorm2d, compute_dtype=None):
+        super(PixelDiscriminator, self).__init__()
+        use_bias = _uses_instance_norm(norm_layer)
+        self.net = nn.Sequential(
+            nn.Conv2d(input_nc, ndf, kernel_size=1, stride=1, padding=0),
+            nn.LeakyReLU(0.2, True),
+            nn.Conv2d(ndf, ndf * 2, kernel_size=1, stride=1, padding=0, bias=use_bias),
+            norm_layer(ndf * 2),
+            nn.LeakyReLU(0.2, True),
+            nn.Conv2d(ndf * 2, 1, kernel_size=1, stride=1, padding=0, bias=use_bias))
+        from .pix2pix_engine import DiscriminatorEngine
+        object.__setattr__(self, "_engine", DiscriminatorEngine(self, compute_dtype, seq="net"))
 
     @property
     def engine(self):

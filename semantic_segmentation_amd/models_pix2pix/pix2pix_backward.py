@@ -17,7 +17,7 @@ import torch
 
 from .. import ops
 from .._lib import ACT_LEAKY02, ACT_NONE, ACT_RELU, ACT_TANH
-from .pix2pix_engine import cached_geom, g_tapw_identity
+from .pix2pix_engine import cached_geom, g_tapw_identity, image_conv_dgrad, image_conv_wgrad
 
 TAPS64 = tuple((ky - 3, kx - 3) for ky in range(8) for kx in range(8))
 
@@ -182,12 +182,9 @@ def generator_backward(engine, ctx, arch, dout, need_dx):
                         dz_b=dL, act_b=ACT_LEAKY02, inorm=lv.get("inorm"))
         bias_grad(conv, dy, lv.get("inorm") is not None)
         if k == 1:
-            dw = torch.zeros_like(conv.weight, memory_format=torch.contiguous_format)
-            ops.conv_smallcin_wgrad(ctx["x"], dy, dw, 4, 2, 1, inv_s)
-            emit(conv.weight, dw)
+            emit(conv.weight, image_conv_wgrad(ctx["x"], dy, conv, 4, 2, 1, inv_s))
             if need_dx:
-                dx = torch.empty_like(ctx["x"])
-                ops.conv_smallcin_dgrad(dy, conv.weight.detach().contiguous(), dx, 4, 2, 1, inv_s)
+                dx = image_conv_dgrad(dy, conv, ctx["x"], 4, 2, 1, inv_s)
         else:
             cin, cout = c[k - 1], c[k]
             # K parts in slabs + ordered reduction fused with scale / unpack (one part: a plain store): deterministic

@@ -11,6 +11,9 @@ Generator (reference models_pix2pix/networks.py:514-617, 8 levels at 256x256):
     transposed conv (exact; csrc/pix2pix.hip), split into 4 sub-pixel classes of 16 taps on the MFMA engine;
     BN (+dropout keep-mask) + ReLU write into the second half of R_{k-1}.
 Discriminator (:620-665): direct 2->64 conv, three MFMA convs with BN+LeakyReLU, direct 512->1 head (fp32 logits).
+PixelDiscriminator (:668-697) is the same stage list with 1x1 kernels and runs on DiscriminatorEngine(seq="net").
+Images of 5..16 channels (an RGB pair is six; one-hot masks into the generator): the image-side conv, its weight and data gradient
+are the fp32-MFMA kernels of csrc/ends_wide.hip (image_conv_* below) instead of the direct ones; 1..4 channels launch what they did.
 Gradients are carried multiplied by a power-of-two scale (see unet_engine.py).
 `--norm instance` (InstanceNorm2d without parameters or running statistics, networks.py:23-38): the same plans with the norm's
 statistics per (sample, channel) from gs_in_stats after each normed conv (train and eval alike) and gs_in_act_apply in place of
@@ -50,6 +53,48 @@ def _bias32(conv):
 def _need_cuda(x):
     if not x.is_cuda:
         raise RuntimeError("semantic_segmentation_amd Pix2Pix networks run on the MI355X only (no CPU / ATen fallback)")
+
+
+IMAGE_NC_MAX = 16           # image channels of the first-layer kernels: 1..4 csrc/direct.hip, 5..16 csrc/ends_wide.hip
+
+
+def _check_image_conv(who, cin, cout):
+    """the refusals of the image-side conv, raised before any launch (and before the device check)"""
+    if cin > IMAGE_NC_MAX:
+        raise NotImplementedError(f"{who} input_nc {cin} is not supported: the first-layer kernels take up to {IMAGE_NC_MAX} image channels")
+    if cin > 4 and (cout % 8 != 0 or cout > 128):
+        raise NotImplementedError(f"{who} with input_nc {cin} (5..{IMAGE_NC_MAX}) needs a first layer of a multiple of 8 and at most 128 "
+                                  f"output channels, got {cout}")
+
+
+def image_conv_fwd(x, conv, y, k, s, p, act):
+    """the conv on the fp32 NCHW image: direct kernel for 1..4 channels, the fp32-MFMA kernel for 5..16"""
+    w = conv.weight.detach().contiguous()
+    b = _bias32(conv)
+    if x.shape[1] > 4:
+        ops.conv_imgwide_fwd(x, w, b, y, k, s, p, act)
+    else:
+        ops.conv_smallcin_fwd(x, w, b, y, None, k, s, p, act)
+
+
+def image_conv_wgrad(x, dy, conv, k, s, p, inv_s):
+    if x.shape[1] > 4:
+        dw = torch.empty_like(conv.weight, memory_format=torch.contiguous_format)
+        ops.conv_imgwide_wgrad(x, dy, dw, k, s, p, inv_s)
+    else:
+        dw = torch.zeros_like(conv.weight, memory_format=torch.contiguous_format)
+        ops.conv_smallcin_wgrad(x, dy, dw, k, s, p, inv_s)
+    return dw
+
+
+def image_conv_dgrad(dy, conv, x, k, s, p, inv_s):
+    dx = torch.empty_like(x)
+    w = conv.weight.detach().contiguous()
+    if x.shape[1] > 4:
+        ops.conv_imgwide_dgrad(dy, w, dx, k, s, p, inv_s)
+    else:
+        ops.conv_smallcin_dgrad(dy, w, dx, k, s, p, inv_s)
+    return dx
 
 
 # GSSEG_PIX2PIX_DIRECT_IMAGE=0: run the outermost generator layer on the MFMA engine (4 class launches + tanh + layout pass)
@@ -190,13 +235,12 @@ class GeneratorEngine(ParamIndex):
 
     # -------------------------------------------------------------------------------------------------
     def forward(self, x, arch, training, need_grad, dropout_masks):
+        blocks = self.blocks()
+        _check_image_conv("generator", x.shape[1], self._parts(blocks[0])[0].out_channels)
         _need_cuda(x)
         net, tdt = self.net, self.tdt
-        blocks = self.blocks()
         D = len(blocks)
         N, cin0, H, W = x.shape
-        if cin0 > 4:
-            raise NotImplementedError("generator input_nc above 4 is not supported by the direct first-layer kernel")
         if H % (1 << D) or W % (1 << D):
             raise ValueError(f"input size must be a multiple of {1 << D}")
         dev = x.device
@@ -221,7 +265,7 @@ class GeneratorEngine(ParamIndex):
         # ---- down path -------------------------------------------------------------------------------
         conv0 = parts[0][0]
         y1 = empty(N, hs[1], ws[1], c[1])
-        ops.conv_smallcin_fwd(x, conv0.weight.detach().contiguous(), _bias32(conv0), y1, None, 4, 2, 1)
+        image_conv_fwd(x, conv0, y1, 4, 2, 1, ACT_NONE)
         L[1] = empty(N, hs[1], ws[1], c[1])
         R[1] = empty(N, hs[1], ws[1], 2 * c[1])
         ops.bn_act_apply(y1, None, None, ACT_LEAKY02, L[1], c[1], 0)
@@ -420,8 +464,11 @@ class _GeneratorFunction(torch.autograd.Function):
 # Discriminator
 # =====================================================================================================
 class DiscriminatorEngine(ParamIndex):
-    def __init__(self, net, dtype=None):
+    def __init__(self, net, dtype=None, seq="model"):
+        """seq: the attribute of `net` that holds the reference's Sequential: `model` (NLayerDiscriminator, networks.py:661) or
+        `net` (PixelDiscriminator, :693 -- the same conv / norm / LeakyReLU stages with 1x1 kernels, so the same plan)"""
         self.net = net
+        self.seq = seq
         self.dtype, self.tdt = compute_dtype(dtype)
         self.packs = _PackCache()
         self.trust_versions = False      # see engine_common.pack_reuse_allowed
@@ -433,7 +480,7 @@ class DiscriminatorEngine(ParamIndex):
         return _DiscriminatorFunction.apply(self, self.net.training, need_grad, x, *params)
 
     def layout(self):
-        seq = list(self.net.model)
+        seq = list(getattr(self.net, self.seq))
         convs = [(i, m) for i, m in enumerate(seq) if isinstance(m, torch.nn.Conv2d)]
         stages = []
         for idx, (i, conv) in enumerate(convs):
@@ -442,16 +489,16 @@ class DiscriminatorEngine(ParamIndex):
         return stages
 
     def forward(self, x, training, need_grad):
+        stages = self.layout()
+        _check_image_conv("discriminator", x.shape[1], stages[0][1].out_channels)
         _need_cuda(x)
         tdt = self.tdt
         dev = x.device
         x = x.contiguous().float()
         N, cin0, H, W = x.shape
-        stages = self.layout()
+        sq = self.seq
         if not pack_reuse_allowed(need_grad, self.trust_versions):
             self.packs.clear()       # training forwards always re-pack: `.data` writes (Betty) bump no version counter
-        if cin0 > 4:
-            raise NotImplementedError("discriminator input_nc above 4 is not supported by the direct first-layer kernel")
 
         def empty(*shape, dtype=tdt):
             return torch.empty(shape, dtype=dtype, device=dev)
@@ -463,7 +510,7 @@ class DiscriminatorEngine(ParamIndex):
             cw = ops.conv_out_size(cw, conv.kernel_size[0], conv.stride[0], conv.padding[0])
             if is_instance_norm(bn) and ch * cw < 2:
                 raise ValueError(f"Expected more than 1 spatial element when training, got input size "
-                                 f"{[N, conv.out_channels, ch, cw]} (InstanceNorm2d model.{i + 1})")
+                                 f"{[N, conv.out_channels, ch, cw]} (InstanceNorm2d {sq}.{i + 1})")
         recs = []
         nbt_pending = []
         # stage 0: direct conv + bias + LeakyReLU (no norm)
@@ -471,9 +518,8 @@ class DiscriminatorEngine(ParamIndex):
         k, s, p = conv0.kernel_size[0], conv0.stride[0], conv0.padding[0]
         h, w = ops.conv_out_size(H, k, s, p), ops.conv_out_size(W, k, s, p)
         z = empty(N, h, w, conv0.out_channels)
-        ops.conv_smallcin_fwd(x, conv0.weight.detach().contiguous(),
-                              conv0.bias.detach() if conv0.bias is not None else None, z, None, k, s, p, ACT_LEAKY02)
-        recs.append(dict(kind="first", conv=conv0, x=x, z=z, k=k, s=s, p=p, name=f"model.{i0}"))
+        image_conv_fwd(x, conv0, z, k, s, p, ACT_LEAKY02)
+        recs.append(dict(kind="first", conv=conv0, x=x, z=z, k=k, s=s, p=p, name=f"{sq}.{i0}"))
         cur, ch, cw, cc = z, h, w, conv0.out_channels
         for (i, conv, bn) in stages[1:-1]:
             k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
@@ -491,7 +537,7 @@ class DiscriminatorEngine(ParamIndex):
                 mi = instance_stats(y, bn)
                 ops.in_act_apply(y, mi[0], mi[1], ACT_LEAKY02, z, conv.out_channels, 0)
                 recs.append(dict(kind="mid", conv=conv, bn=bn, inp=cur, y=y, coef=None, stats=True, inorm=mi, geom=g, wd=wd,
-                                 k=k, s=s, p=p, ih=ch, iw=cw, cin=cc, name=f"model.{i}", bnname=f"model.{i + 1}"))
+                                 k=k, s=s, p=p, ih=ch, iw=cw, cin=cc, name=f"{sq}.{i}", bnname=f"{sq}.{i + 1}"))
                 cur, ch, cw, cc = z, oh, ow, conv.out_channels
                 continue
             mt = ops.conv_igemm_mtiles(g)
@@ -501,7 +547,7 @@ class DiscriminatorEngine(ParamIndex):
             coef, stats = bn_coeffs(bn, part, mt, conv.out_channels, N * oh * ow, training, dev, nbt_pending)
             ops.bn_act_apply(y, coef[0], coef[1], ACT_LEAKY02, z, conv.out_channels, 0)
             recs.append(dict(kind="mid", conv=conv, bn=bn, inp=cur, y=y, coef=coef, stats=stats, geom=g, wd=wd,
-                             k=k, s=s, p=p, ih=ch, iw=cw, cin=cc, name=f"model.{i}", bnname=f"model.{i + 1}"))
+                             k=k, s=s, p=p, ih=ch, iw=cw, cin=cc, name=f"{sq}.{i}", bnname=f"{sq}.{i + 1}"))
             cur, ch, cw, cc = z, oh, ow, conv.out_channels
         il, convl, _ = stages[-1]
         k, s, p = convl.kernel_size[0], convl.stride[0], convl.padding[0]
@@ -509,7 +555,7 @@ class DiscriminatorEngine(ParamIndex):
         logits = torch.empty((N, convl.out_channels, oh, ow), dtype=torch.float32, device=dev)
         ops.conv_smallcout_fwd(cur, convl.weight.detach().contiguous(),
                                convl.bias.detach() if convl.bias is not None else None, logits, k, s, p)
-        recs.append(dict(kind="last", conv=convl, inp=cur, k=k, s=s, p=p, ih=ch, iw=cw, cin=cc, name=f"model.{il}"))
+        recs.append(dict(kind="last", conv=convl, inp=cur, k=k, s=s, p=p, ih=ch, iw=cw, cin=cc, name=f"{sq}.{il}"))
         _flush_nbt(nbt_pending)
         return logits, (dict(recs=recs, N=N, H=H, W=W) if need_grad else None)
 
@@ -609,9 +655,7 @@ class DiscriminatorEngine(ParamIndex):
         dy = empty(*z.shape)
         # z = leaky(conv + bias): the activation gradient only needs the sign, which z preserves
         ops.bn_act_bwd_apply(z, dz, z.shape[3], 0, None, None, None, None, None, None, None, ACT_LEAKY02, False, dy)
-        dw = torch.zeros_like(conv.weight, memory_format=torch.contiguous_format)
-        ops.conv_smallcin_wgrad(first["x"], dy, dw, first["k"], first["s"], first["p"], inv_s)
-        grads[first["name"] + ".weight"] = dw
+        grads[first["name"] + ".weight"] = image_conv_wgrad(first["x"], dy, conv, first["k"], first["s"], first["p"], inv_s)
         if conv.bias is not None:
             ws = empty(1024 * z.shape[3], dtype=torch.float32)
             db = empty(z.shape[3], dtype=torch.float32)
@@ -619,8 +663,7 @@ class DiscriminatorEngine(ParamIndex):
             grads[first["name"] + ".bias"] = db
         dx = None
         if need_dx:
-            dx = torch.empty_like(first["x"])
-            ops.conv_smallcin_dgrad(dy, conv.weight.detach().contiguous(), dx, first["k"], first["s"], first["p"], inv_s)
+            dx = image_conv_dgrad(dy, conv, first["x"], first["k"], first["s"], first["p"], inv_s)
         if self.after_backward is not None:
             self.after_backward()
         return emitter.grads, dx

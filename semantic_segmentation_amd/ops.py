@@ -1887,3 +1887,57 @@ def maxpool3d_fwd_pair_q8(z_hi, z_lo, z_q8, zq_coff, z_stride, zp_hi, zp_lo, zp_
     zq_coff; zp_q8 -> zp_lo is the pooled buffer's q plane."""
     _lib.call("gs_maxpool3d_fwd_pair_q8", _p(z_hi), _p(z_lo), int(bool(z_q8)), zq_coff, z_stride, _p(zp_hi), _p(zp_lo), int(bool(zp_q8)),
               zp_stride, NB, D, H, W, C, dt_code(z_hi), _stream())
+
+
+# ---------------------------------------------------------------------------- image-side convs of 5..16 channels (csrc/ends_wide.hip)
+def _imgwide_shapes(who, x_shape, w, t16, k, stride, pad):
+    N, Cin, IH, IW = x_shape
+    if t16.dim() != 4 or not t16.is_contiguous() or t16.shape[0] != N:
+        raise ValueError(f"{who}: the 16-bit tensor must be dense [N,OH,OW,Cout]")
+    _, OH, OW, Cout = t16.shape
+    if tuple(w.shape) != (Cout, Cin, k, k):
+        raise ValueError(f"{who}: w must be [Cout={Cout}, Cin={Cin}, {k}, {k}], got {tuple(w.shape)}")
+    return N, Cin, IH, IW, Cout, OH, OW
+
+
+def _imgwide_call(name, Cin, Cout, k, stride, pad, *args):
+    rc = getattr(_lib.load(), name)(*args)
+    if rc == _lib.GS_EUNSUPPORTED:
+        raise NotImplementedError(f"{name}: Cin={Cin} (5..16), Cout={Cout} (a multiple of 8 up to 128), k/stride/pad={k}/{stride}/{pad} "
+                                  "(4/2/1 or 1/1/0) not covered")
+    _lib.check(rc, name)
+
+
+def conv_imgwide_fwd(x, w, bias, y, k, stride, pad, act=ACT_NONE):
+    """y [N,OH,OW,Cout] 16-bit = act(conv(x fp32 [N,Cin,IH,IW], w fp32 [Cout,Cin,k,k]) + bias), Cin 5..16; act ACT_NONE / ACT_LEAKY02."""
+    _dev(x)
+    _f32(x, "x"); _f32(w, "w"); _f32(bias, "bias")
+    N, Cin, IH, IW, Cout, OH, OW = _imgwide_shapes("conv_imgwide_fwd", x.shape, w, y, k, stride, pad)
+    _imgwide_call("gs_conv_imgwide_fwd", Cin, Cout, k, stride, pad, _p(x), _p(w), _p(bias), _p(y), N, Cin, IH, IW, Cout, OH, OW,
+                  k, stride, pad, act, dt_code(y), _stream())
+
+
+def conv_imgwide_wgrad_ws(N, OH, OW, Cin, Cout, k, dev):
+    return torch.empty(int(_lib.load().gs_conv_imgwide_wgrad_ws_floats(N, OH, OW, Cin, Cout, k)), dtype=torch.float32, device=dev)
+
+
+def conv_imgwide_wgrad(x, dy, dw, k, stride, pad, gscale, ws=None):
+    """dw fp32 [Cout,Cin,k,k] = gscale * sum dy * x (overwrites; deterministic slab reduction)."""
+    _dev(x)
+    _f32(x, "x"); _f32(dw, "dw"); _f32(ws, "ws")
+    N, Cin, IH, IW, Cout, OH, OW = _imgwide_shapes("conv_imgwide_wgrad", x.shape, dw, dy, k, stride, pad)
+    if ws is None:
+        ws = conv_imgwide_wgrad_ws(N, OH, OW, Cin, Cout, k, x.device)
+    elif ws.numel() < int(_lib.load().gs_conv_imgwide_wgrad_ws_floats(N, OH, OW, Cin, Cout, k)):
+        raise ValueError("conv_imgwide_wgrad: ws needs gs_conv_imgwide_wgrad_ws_floats floats")
+    _imgwide_call("gs_conv_imgwide_wgrad", Cin, Cout, k, stride, pad, _p(x), _p(dy), _p(dw), _p(ws), N, Cin, IH, IW, Cout, OH, OW,
+                  k, stride, pad, float(gscale), dt_code(dy), _stream())
+
+
+def conv_imgwide_dgrad(dy, w, dx, k, stride, pad, gscale):
+    """dx fp32 [N,Cin,IH,IW] = gscale * conv_transpose(dy, w) (overwrites)."""
+    _dev(dy)
+    _f32(w, "w"); _f32(dx, "dx")
+    N, Cin, IH, IW, Cout, OH, OW = _imgwide_shapes("conv_imgwide_dgrad", dx.shape, w, dy, k, stride, pad)
+    _imgwide_call("gs_conv_imgwide_dgrad", Cin, Cout, k, stride, pad, _p(dy), _p(w), _p(dx), N, Cin, IH, IW, Cout, OH, OW,
+                  k, stride, pad, float(gscale), dt_code(dy), _stream())
