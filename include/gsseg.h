@@ -872,6 +872,43 @@ int gs_conv_imgwide_wgrad(const float* x, const void* dy, float* dw, float* ws, 
 int gs_conv_imgwide_dgrad(const void* dy, const float* w, float* dx, int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int k,
                           int stride, int pad, float gscale, int dtype, void* stream);
 
+/* The two ends of the 3-D Pix2Pix discriminators (csrc/ends3d.hip; GenSeg-3D/models/networks.py:806-890 with a 3-D norm layer).  A
+ * volume is a stack of depth slices: the 16-bit tensors are dense [N*D,H,W,C].
+ *
+ * Image side -- NLayerDiscriminator.model.0 (GenSeg-3D/models/networks.py:829, Conv3d k 4 / stride 2 / pad 1) and
+ * PixelDiscriminator.net.0 (:879, Conv3d k 1 / stride 1 / pad 0) -- between an fp32 NCDHW volume [N,Cin,ID,IH,IW], Cin 1..16, and a
+ * dense 16-bit tensor [N*OD,OH,OW,Cout], Cout any multiple of 8 up to 128; w is the module's fp32 weight [Cout][Cin][k][k][k].  The
+ * volume is not rounded to 16 bits; products are fp32 x fp32 accumulated in fp32 (v_mfma_f32_32x32x2_f32 in the forward and the
+ * weight gradient).  Checked before any launch: GS_EINVAL for a null or misaligned pointer (16 bytes for the 16-bit tensor, 4 for
+ * fp32), a bad dtype or volumes that do not match; GS_EUNSUPPORTED for Cin outside 1..16, Cout not a multiple of 8 or above 128, or
+ * another (k, stride, pad).
+ * gs_conv3d_img_fwd  : y = act(conv3d(x, w) + bias); bias may be NULL; act GS_ACT_NONE or GS_ACT_LEAKY02 (else GS_EUNSUPPORTED).
+ * gs_conv3d_img_wgrad: dw [Cout][Cin][k][k][k] = gscale * sum over voxels of dy * x (overwrites).  ws: gs_conv3d_img_wgrad_ws_floats
+ *   floats of per-block partial slabs, added in slab order by a second launch: no atomics, two runs give equal bits.  (The bias
+ *   gradient of these layers is gs_colsum over dy.)
+ * gs_conv3d_img_dgrad: dx fp32 NCDHW [N,Cin,ID,IH,IW] = gscale * conv_transpose3d(dy, w) (overwrites every element). */
+int gs_conv3d_img_fwd(const float* x, const float* w, const float* bias, void* y, int N, int Cin, int ID, int IH, int IW, int Cout,
+                      int OD, int OH, int OW, int k, int stride, int pad, int act, int dtype, void* stream);
+int64_t gs_conv3d_img_wgrad_ws_floats(int N, int OD, int OH, int OW, int Cin, int Cout, int k);
+int gs_conv3d_img_wgrad(const float* x, const void* dy, float* dw, float* ws, int N, int Cin, int ID, int IH, int IW, int Cout, int OD,
+                        int OH, int OW, int k, int stride, int pad, float gscale, int dtype, void* stream);
+int gs_conv3d_img_dgrad(const void* dy, const float* w, float* dx, int N, int Cin, int ID, int IH, int IW, int Cout, int OD, int OH,
+                        int OW, int k, int stride, int pad, float gscale, int dtype, void* stream);
+
+/* One-channel head -- the last conv of NLayerDiscriminator (GenSeg-3D/models/networks.py:850, Conv3d(C, 1, k 4, stride 1, pad 1)) and
+ * of PixelDiscriminator (:884, Conv3d(C, 1, k 1)) -- on the contract of gs_conv_smallcout_fwd / _bwd: x 16-bit [N*D,H,W,Cin], Cin a
+ * multiple of 8 up to 1024 (else GS_EUNSUPPORTED, as for another (k, pad) than (4, 1) / (1, 0)); w fp32 [1][Cin][k][k][k]; logits
+ * fp32 [N,1,OD,OH,OW], OD = D + 2 pad - k + 1.  The forward is a reduction (one block per logit for k 4), bias may be NULL.
+ * gs_conv3d_head_bwd: dl fp32 [N,1,OD,OH,OW] (already times the loss scale) -> dz 16-bit [N*D,H,W,Cin], the tap sum in fp32 rounded
+ *   once; dw [1][Cin][k][k][k] and db [1] += gscale * sums (fp32, ACCUMULATE as gs_conv_smallcout_bwd does) through per-part slabs in
+ *   ws (gs_conv3d_head_bwd_ws_floats floats) added in part order: no atomics, two runs give equal bits.  dz may be NULL; dw and db
+ *   may be NULL together (then x and ws are not read). */
+int gs_conv3d_head_fwd(const void* x, const float* w, const float* bias, float* y, int N, int D, int H, int W, int Cin, int OD, int OH,
+                       int OW, int k, int pad, int dtype, void* stream);
+int64_t gs_conv3d_head_bwd_ws_floats(int N, int OD, int OH, int OW, int Cin, int k);
+int gs_conv3d_head_bwd(const void* x, const float* w, const float* dl, void* dz, float* dw, float* db, float* ws, int N, int D, int H,
+                       int W, int Cin, int OD, int OH, int OW, int k, int pad, float gscale, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,13 @@ PROTOTYPES = {
     "gs_conv_imgwide_wgrad_ws_floats": (c_int64, [c_int] * 6),
     "gs_conv_imgwide_wgrad": (c_int, [_F, _P, _F, _F] + [c_int] * 10 + [c_float, c_int, c_void_p]),
     "gs_conv_imgwide_dgrad": (c_int, [_P, _F, _F] + [c_int] * 10 + [c_float, c_int, c_void_p]),
+    "gs_conv3d_img_fwd": (c_int, [_F, _F, _F, _P] + [c_int] * 14 + [c_void_p]),
+    "gs_conv3d_img_wgrad_ws_floats": (c_int64, [c_int] * 7),
+    "gs_conv3d_img_wgrad": (c_int, [_F, _P, _F, _F] + [c_int] * 12 + [c_float, c_int, c_void_p]),
+    "gs_conv3d_img_dgrad": (c_int, [_P, _F, _F] + [c_int] * 12 + [c_float, c_int, c_void_p]),
+    "gs_conv3d_head_fwd": (c_int, [_P, _F, _F, _F] + [c_int] * 11 + [c_void_p]),
+    "gs_conv3d_head_bwd_ws_floats": (c_int64, [c_int] * 6),
+    "gs_conv3d_head_bwd": (c_int, [_P, _F, _F, _P, _F, _F, _F] + [c_int] * 10 + [c_float, c_int, c_void_p]),
 }
 
 _lib = None

@@ -22,13 +22,14 @@ class Identity(nn.Module):
         return x
 
 
-def get_norm_layer(norm_type='instance'):
+def get_norm_layer(norm_type='instance', threed=False):
     """networks.py:23-41.  'batch' (the pix2pix default, pix2pix_model.py:34) and 'instance' (the default of --norm,
-    options/base_options.py:36) run on the HIP engine."""
+    options/base_options.py:36) run on the HIP engine.  threed (GenSeg-3D/models/networks.py:109-131): the BatchNorm3d /
+    InstanceNorm3d partials, from which the discriminators build their 3-D form."""
     if norm_type == 'batch':
-        return functools.partial(nn.BatchNorm2d, affine=True, track_running_stats=True)
+        return functools.partial(nn.BatchNorm3d if threed else nn.BatchNorm2d, affine=True, track_running_stats=True)
     if norm_type == 'instance':
-        return functools.partial(nn.InstanceNorm2d, affine=False, track_running_stats=False)
+        return functools.partial(nn.InstanceNorm3d if threed else nn.InstanceNorm2d, affine=False, track_running_stats=False)
     if norm_type == 'none':
         return lambda x: Identity()
     raise NotImplementedError('normalization layer [%s] is not found' % norm_type)
@@ -51,7 +52,7 @@ def init_weights(net, init_type='normal', init_gain=0.02):
                 raise NotImplementedError('initialization method [%s] is not implemented' % init_type)
             if hasattr(m, 'bias') and m.bias is not None:
                 init.constant_(m.bias.data, 0.0)
-        elif classname.find('BatchNorm2d') != -1:
+        elif classname.find('BatchNorm2d') != -1 or classname.find('BatchNorm3d') != -1:
             init.normal_(m.weight.data, 1.0, init_gain)
             init.constant_(m.bias.data, 0.0)
     net.apply(init_func)
@@ -84,8 +85,9 @@ def define_G(input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, in
     return init_net(net, init_type, init_gain, gpu_ids)
 
 
-def define_D(input_nc, ndf, netD, n_layers_D=3, norm='batch', init_type='normal', init_gain=0.02, gpu_ids=[]):
-    norm_layer = get_norm_layer(norm_type=norm)
+def define_D(input_nc, ndf, netD, n_layers_D=3, norm='batch', init_type='normal', init_gain=0.02, gpu_ids=[], threed=False):
+    """threed (GenSeg-3D/models/networks.py:265-311): the discriminators on volumes [N,C,D,H,W] (Conv3d leaves, 3-D norms)"""
+    norm_layer = get_norm_layer(norm_type=norm, threed=threed)
     if netD == 'basic':
         net = NLayerDiscriminator(input_nc, ndf, n_layers=3, norm_layer=norm_layer)
     elif netD == 'n_layers':
@@ -156,6 +158,28 @@ def _uses_instance_norm(norm_layer):
     for flag in ("affine", "track_running_stats"):
         if getattr(probe, flag):
             raise NotImplementedError("InstanceNorm2d with %s=True is not on the MI355X hot path (get_norm_layer('instance') "
+                                      "builds affine=False, track_running_stats=False)" % flag)
+    return True
+
+
+def is_threed_layer(norm_layer):
+    """GenSeg-3D/models/networks.py:89-93: the norm layer decides whether a discriminator is built on volumes"""
+    func = norm_layer.func if type(norm_layer) == functools.partial else norm_layer
+    return getattr(func, "__name__", "").find("3d") > -1
+
+
+def add_bias(norm_layer, threed):
+    """GenSeg-3D/models/networks.py:96-106: a conv in front of a norm carries a bias only under InstanceNorm (of the network's
+    dimension).  As in 2-D the engine runs the InstanceNorm get_norm_layer builds (no parameters, no buffers) and no other."""
+    if not threed:
+        return _uses_instance_norm(norm_layer)
+    func = norm_layer.func if type(norm_layer) == functools.partial else norm_layer
+    if func != nn.InstanceNorm3d:
+        return False
+    probe = norm_layer(8)
+    for flag in ("affine", "track_running_stats"):
+        if getattr(probe, flag):
+            raise NotImplementedError("InstanceNorm3d with %s=True is not on the MI355X hot path (get_norm_layer('instance', threed=True) "
                                       "builds affine=False, track_running_stats=False)" % flag)
     return True
 
@@ -321,25 +345,34 @@ class ResnetGenerator(nn.Module):
 
 
 class NLayerDiscriminator(nn.Module):
-    """networks.py:620-665 PatchGAN (same Sequential indices: convs at 0,2,5,8,11; norms at 3,6,9)."""
+    """networks.py:620-665 PatchGAN (same Sequential indices: convs at 0,2,5,8,11; norms at 3,6,9).  With a 3-D norm layer
+    (GenSeg-3D/models/networks.py:806-855) the leaves are nn.Conv3d -- same indices, 5-D weights -- and the plan is
+    pix2pix3d_engine.Discriminator3DEngine."""
 
     def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, compute_dtype=None):
         super(NLayerDiscriminator, self).__init__()
-        use_bias = _uses_instance_norm(norm_layer)
+        threed = is_threed_layer(norm_layer)
+        use_bias = add_bias(norm_layer, threed)
+        conv_layer = nn.Conv3d if threed else nn.Conv2d
         kw, padw = 4, 1
-        sequence = [nn.Conv2d(input_nc, ndf, kernel_size=kw, stride=2, padding=padw), nn.LeakyReLU(0.2, True)]
+        sequence = [conv_layer(input_nc, ndf, kernel_size=kw, stride=2, padding=padw), nn.LeakyReLU(0.2, True)]
         nf_mult = 1
         for n in range(1, n_layers):
             nf_mult_prev, nf_mult = nf_mult, min(2 ** n, 8)
-            sequence += [nn.Conv2d(ndf * nf_mult_prev, ndf * nf_mult, kernel_size=kw, stride=2, padding=padw,
-                                   bias=use_bias), norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True)]
+            sequence += [conv_layer(ndf * nf_mult_prev, ndf * nf_mult, kernel_size=kw, stride=2, padding=padw,
+                                    bias=use_bias), norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True)]
         nf_mult_prev, nf_mult = nf_mult, min(2 ** n_layers, 8)
-        sequence += [nn.Conv2d(ndf * nf_mult_prev, ndf * nf_mult, kernel_size=kw, stride=1, padding=padw,
-                               bias=use_bias), norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True)]
-        sequence += [nn.Conv2d(ndf * nf_mult, 1, kernel_size=kw, stride=1, padding=padw)]
+        sequence += [conv_layer(ndf * nf_mult_prev, ndf * nf_mult, kernel_size=kw, stride=1, padding=padw,
+                                bias=use_bias), norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True)]
+        sequence += [conv_layer(ndf * nf_mult, 1, kernel_size=kw, stride=1, padding=padw)]
         self.model = nn.Sequential(*sequence)
-        from .pix2pix_engine import DiscriminatorEngine
-        object.__setattr__(self, "_engine", DiscriminatorEngine(self, compute_dtype))
+        self.threed = threed
+        if threed:
+            from .pix2pix3d_engine import Discriminator3DEngine
+            object.__setattr__(self, "_engine", Discriminator3DEngine(self, compute_dtype))
+        else:
+            from .pix2pix_engine import DiscriminatorEngine
+            object.__setattr__(self, "_engine", DiscriminatorEngine(self, compute_dtype))
 
     @property
     def engine(self):
@@ -355,16 +388,23 @@ class PixelDiscriminator(nn.Module):
 
     def __init__(self, input_nc, ndf=64, norm_layer=nn.BatchNorm2d, compute_dtype=None):
         super(PixelDiscriminator, self).__init__()
-        use_bias = _uses_instance_norm(norm_layer)
+        threed = is_threed_layer(norm_layer)                   # GenSeg-3D/models/networks.py:858-886: Conv3d leaves, same indices
+        use_bias = add_bias(norm_layer, threed)
+        conv_layer = nn.Conv3d if threed else nn.Conv2d
         self.net = nn.Sequential(
-            nn.Conv2d(input_nc, ndf, kernel_size=1, stride=1, padding=0),
+            conv_layer(input_nc, ndf, kernel_size=1, stride=1, padding=0),
             nn.LeakyReLU(0.2, True),
-            nn.Conv2d(ndf, ndf * 2, kernel_size=1, stride=1, padding=0, bias=use_bias),
+            conv_layer(ndf, ndf * 2, kernel_size=1, stride=1, padding=0, bias=use_bias),
             norm_layer(ndf * 2),
             nn.LeakyReLU(0.2, True),
-            nn.Conv2d(ndf * 2, 1, kernel_size=1, stride=1, padding=0, bias=use_bias))
-        from .pix2pix_engine import DiscriminatorEngine
-        object.__setattr__(self, "_engine", DiscriminatorEngine(self, compute_dtype, seq="net"))
+            conv_layer(ndf * 2, 1, kernel_size=1, stride=1, padding=0, bias=use_bias))
+        self.threed = threed
+        if threed:
+            from .pix2pix3d_engine import Discriminator3DEngine
+            object.__setattr__(self, "_engine", Discriminator3DEngine(self, compute_dtype, seq="net"))
+        else:
+            from .pix2pix_engine import DiscriminatorEngine
+            object.__setattr__(self, "_engine", DiscriminatorEngine(self, compute_dtype, seq="net"))
 
     @property
     def engine(self):

@@ -490,6 +490,9 @@ class DiscriminatorEngine(ParamIndex):
 
     def forward(self, x, training, need_grad):
         stages = self.layout()
+        if x.dim() != 4:
+            raise ValueError(f"a 2-D discriminator takes an image batch [N,C,H,W], got a {x.dim()}-D tensor {tuple(x.shape)} "
+                             "(volumes: define_D(..., threed=True))")
         _check_image_conv("discriminator", x.shape[1], stages[0][1].out_channels)
         _need_cuda(x)
         tdt = self.tdt

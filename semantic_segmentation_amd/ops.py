@@ -202,6 +202,53 @@ def geom_conv_s2_dgrad_class(N, IH, IW, Cin, Cout, k, pad, py, px, **kw) -> GsCo
     return make_geom(N, OH, OW, Cout, ihg, iwg, Cin, IH, IW, taps, osy=2, osx=2, ooy=py, oox=px, tap_w=slots, **kw)
 
 
+# Conv3d on depth-slice stacks [N*D,H,W,C]: the 2-D builders with a depth axis (GsConvGeom.Dg / Din / Dout / isz / osz / ooz / tap_dz).
+# Weight slot of tap (kz,ky,kx) = (kz*k + ky)*k + kx: a [Cout][Cin][k][k][k] tensor VIEWED as [Cout][Cin][k*k][k] goes through
+# pack_weight / conv_wgrad_det unchanged (they see k*k*k taps in the tensor's own order) -- conv3d_weight_view().
+def conv3d_weight_view(w: torch.Tensor) -> torch.Tensor:
+    """[A][B][k][k][k] -> the 4-D view [A][B][k*k][k] pack_weight takes (same memory, slot (kz*k + ky)*k + kx)"""
+    if w.dim() != 5 or not w.is_contiguous():
+        raise ValueError("conv3d_weight_view: a contiguous 5-D weight")
+    A, B, k = w.shape[0], w.shape[1], w.shape[2]
+    return w.view(A, B, k * k, k)
+
+
+def _taps3d(k):
+    return [(kz, ky, kx) for kz in range(k) for ky in range(k) for kx in range(k)]
+
+
+def geom_conv3d(N, D, IH, IW, Cin, Cout, k, stride, pad, **kw) -> GsConvGeom:
+    """nn.Conv3d(k, stride, pad) on x [N*D,IH,IW,Cin] -> y [N*OD,OH,OW,Cout]: taps in (kz,ky,kx) row-major order, weights
+    [k*k*k][Cout][Cin]; k*k*k <= 64 taps (k <= 4)."""
+    OD, OH, OW = conv_out_size(D, k, stride, pad), conv_out_size(IH, k, stride, pad), conv_out_size(IW, k, stride, pad)
+    t3 = _taps3d(k)
+    return make_geom(N, IH, IW, Cin, OH, OW, Cout, OH, OW, [(ky - pad, kx - pad) for (_, ky, kx) in t3], isy=stride, isx=stride,
+                     tap_dz=[kz - pad for (kz, _, _) in t3], Dg=OD, Din=D, Dout=OD, isz=stride, **kw)
+
+
+def geom_conv3d_dgrad_s1(N, D, IH, IW, Cin, Cout, k, pad, **kw) -> GsConvGeom:
+    """Data gradient of a stride-1 Conv3d as a convolution over dy: dx[i] = sum_t dy[i + pad - k_t] Wd[t], every axis alike.
+    'Input' of this launch is dy [N*OD,OH,OW,Cout]; 'output' is dx [N*D,IH,IW,Cin]; weights [k*k*k][Cin][Cout]."""
+    OD, OH, OW = conv_out_size(D, k, 1, pad), conv_out_size(IH, k, 1, pad), conv_out_size(IW, k, 1, pad)
+    t3 = _taps3d(k)
+    return make_geom(N, OH, OW, Cout, IH, IW, Cin, IH, IW, [(pad - ky, pad - kx) for (_, ky, kx) in t3],
+                     tap_dz=[pad - kz for (kz, _, _) in t3], Dg=D, Din=OD, Dout=D, **kw)
+
+
+def geom_conv3d_s2_dgrad_class(N, D, IH, IW, Cin, Cout, k, pad, pz, py, px, **kw) -> GsConvGeom:
+    """Data gradient of Conv3d(k, stride 2, pad) for input voxels (2a+pz, 2i+py, 2j+px): reads dy [N*OD,OH,OW,Cout] at
+    (a + (pz+pad-kz)/2, ...) for kz == pz+pad (mod 2), rows and columns alike: (k/2)^3 taps of the [k*k*k][Cin][Cout] dgrad pack."""
+    OD, OH, OW = conv_out_size(D, k, 2, pad), conv_out_size(IH, k, 2, pad), conv_out_size(IW, k, 2, pad)
+    sel = [(kz, ky, kx) for (kz, ky, kx) in _taps3d(k)
+           if (pz + pad - kz) % 2 == 0 and (py + pad - ky) % 2 == 0 and (px + pad - kx) % 2 == 0]
+    taps = [((py + pad - ky) // 2, (px + pad - kx) // 2) for (_, ky, kx) in sel]
+    dz = [(pz + pad - kz) // 2 for (kz, _, _) in sel]
+    slots = [(kz * k + ky) * k + kx for (kz, ky, kx) in sel]
+    dg, ihg, iwg = (D - pz + 1) // 2, (IH - py + 1) // 2, (IW - px + 1) // 2
+    return make_geom(N, OH, OW, Cout, ihg, iwg, Cin, IH, IW, taps, osy=2, osx=2, ooy=py, oox=px, tap_w=slots, tap_dz=dz,
+                     Dg=dg, Din=OD, Dout=D, osz=2, ooz=pz, **kw)
+
+
 # ---------------------------------------------------------------------------- MFMA engine
 _SPLITK_WS = collections.OrderedDict()      # (device index, stream handle) -> zeroed fp32 workspace, least recently used first
 _SPLITK_WS_MAX = int(os.environ.get("GSSEG_SPLITK_WS_MAX", "3"))
@@ -1941,3 +1988,106 @@ def conv_imgwide_dgrad(dy, w, dx, k, stride, pad, gscale):
     N, Cin, IH, IW, Cout, OH, OW = _imgwide_shapes("conv_imgwide_dgrad", dx.shape, w, dy, k, stride, pad)
     _imgwide_call("gs_conv_imgwide_dgrad", Cin, Cout, k, stride, pad, _p(dy), _p(w), _p(dx), N, Cin, IH, IW, Cout, OH, OW,
                   k, stride, pad, float(gscale), dt_code(dy), _stream())
+
+
+# ---------------------------------------------------------------------------- the two ends of the 3-D discriminators (csrc/ends3d.hip)
+def _img3d_shapes(who, x_shape, w, t16, k, stride, pad):
+    if len(x_shape) != 5:
+        raise ValueError(f"{who}: the volume must be [N,Cin,D,H,W], got {tuple(x_shape)}")
+    N, Cin, ID, IH, IW = x_shape
+    OD = conv_out_size(ID, k, stride, pad)
+    if t16.dim() != 4 or not t16.is_contiguous() or t16.shape[0] != N * OD:
+        raise ValueError(f"{who}: the 16-bit tensor must be dense [N*OD,OH,OW,Cout]")
+    _, OH, OW, Cout = t16.shape
+    if tuple(w.shape) != (Cout, Cin, k, k, k):
+        raise ValueError(f"{who}: w must be [Cout={Cout}, Cin={Cin}, {k}, {k}, {k}], got {tuple(w.shape)}")
+    return N, Cin, ID, IH, IW, Cout, OD, OH, OW
+
+
+def _img3d_call(name, Cin, Cout, k, stride, pad, *args):
+    rc = getattr(_lib.load(), name)(*args)
+    if rc == _lib.GS_EUNSUPPORTED:
+        raise NotImplementedError(f"{name}: Cin={Cin} (1..16), Cout={Cout} (a multiple of 8 up to 128), k/stride/pad={k}/{stride}/{pad} "
+                                  "(4/2/1 or 1/1/0) not covered")
+    _lib.check(rc, name)
+
+
+def conv3d_img_fwd(x, w, bias, y, k, stride, pad, act=ACT_NONE):
+    """y [N*OD,OH,OW,Cout] 16-bit = act(conv3d(x fp32 [N,Cin,D,H,W], w fp32 [Cout,Cin,k,k,k]) + bias), Cin 1..16; act ACT_NONE /
+    ACT_LEAKY02."""
+    _dev(x)
+    _f32(x, "x"); _f32(w, "w"); _f32(bias, "bias")
+    N, Cin, ID, IH, IW, Cout, OD, OH, OW = _img3d_shapes("conv3d_img_fwd", x.shape, w, y, k, stride, pad)
+    _img3d_call("gs_conv3d_img_fwd", Cin, Cout, k, stride, pad, _p(x), _p(w), _p(bias), _p(y), N, Cin, ID, IH, IW, Cout, OD, OH, OW,
+                k, stride, pad, act, dt_code(y), _stream())
+
+
+def conv3d_img_wgrad_ws(N, OD, OH, OW, Cin, Cout, k, dev):
+    return torch.empty(int(_lib.load().gs_conv3d_img_wgrad_ws_floats(N, OD, OH, OW, Cin, Cout, k)), dtype=torch.float32, device=dev)
+
+
+def conv3d_img_wgrad(x, dy, dw, k, stride, pad, gscale, ws=None):
+    """dw fp32 [Cout,Cin,k,k,k] = gscale * sum dy * x (overwrites; deterministic slab reduction)."""
+    _dev(x)
+    _f32(x, "x"); _f32(dw, "dw"); _f32(ws, "ws")
+    N, Cin, ID, IH, IW, Cout, OD, OH, OW = _img3d_shapes("conv3d_img_wgrad", x.shape, dw, dy, k, stride, pad)
+    if ws is None:
+        ws = conv3d_img_wgrad_ws(N, OD, OH, OW, Cin, Cout, k, x.device)
+    elif ws.numel() < int(_lib.load().gs_conv3d_img_wgrad_ws_floats(N, OD, OH, OW, Cin, Cout, k)):
+        raise ValueError("conv3d_img_wgrad: ws needs gs_conv3d_img_wgrad_ws_floats floats")
+    _img3d_call("gs_conv3d_img_wgrad", Cin, Cout, k, stride, pad, _p(x), _p(dy), _p(dw), _p(ws), N, Cin, ID, IH, IW, Cout, OD, OH, OW,
+                k, stride, pad, float(gscale), dt_code(dy), _stream())
+
+
+def conv3d_img_dgrad(dy, w, dx, k, stride, pad, gscale):
+    """dx fp32 [N,Cin,D,H,W] = gscale * conv_transpose3d(dy, w) (overwrites)."""
+    _dev(dy)
+    _f32(w, "w"); _f32(dx, "dx")
+    N, Cin, ID, IH, IW, Cout, OD, OH, OW = _img3d_shapes("conv3d_img_dgrad", dx.shape, w, dy, k, stride, pad)
+    _img3d_call("gs_conv3d_img_dgrad", Cin, Cout, k, stride, pad, _p(dy), _p(w), _p(dx), N, Cin, ID, IH, IW, Cout, OD, OH, OW,
+                k, stride, pad, float(gscale), dt_code(dy), _stream())
+
+
+def _head3d_shapes(who, t16, w, l, k, pad):
+    if l.dim() != 5 or l.shape[1] != 1 or not l.is_contiguous():
+        raise ValueError(f"{who}: the logits must be contiguous [N,1,OD,OH,OW]")
+    N, _, OD, OH, OW = l.shape
+    D = OD - 2 * pad + k - 1
+    if t16.dim() != 4 or not t16.is_contiguous() or t16.shape[0] != N * D:
+        raise ValueError(f"{who}: the 16-bit tensor must be dense [N*D,H,W,Cin]")
+    _, H, W, Cin = t16.shape
+    if tuple(w.shape) != (1, Cin, k, k, k):
+        raise ValueError(f"{who}: w must be [1, Cin={Cin}, {k}, {k}, {k}], got {tuple(w.shape)}")
+    return N, D, H, W, Cin, OD, OH, OW
+
+
+def _head3d_call(name, Cin, k, pad, *args):
+    rc = getattr(_lib.load(), name)(*args)
+    if rc == _lib.GS_EUNSUPPORTED:
+        raise NotImplementedError(f"{name}: Cin={Cin} (a multiple of 8 up to 1024), k/pad={k}/{pad} (4/1 or 1/0) not covered")
+    _lib.check(rc, name)
+
+
+def conv3d_head_fwd(x, w, bias, y, k, pad):
+    """logits y fp32 [N,1,OD,OH,OW] = conv3d(x 16-bit [N*D,H,W,Cin], w fp32 [1,Cin,k,k,k], stride 1) + bias."""
+    _dev(x)
+    _f32(w, "w"); _f32(bias, "bias"); _f32(y, "y")
+    N, D, H, W, Cin, OD, OH, OW = _head3d_shapes("conv3d_head_fwd", x, w, y, k, pad)
+    _head3d_call("gs_conv3d_head_fwd", Cin, k, pad, _p(x), _p(w), _p(bias), _p(y), N, D, H, W, Cin, OD, OH, OW, k, pad, dt_code(x),
+                 _stream())
+
+
+def conv3d_head_bwd(x, w, dl, dz, dw, db, k, pad, gscale=1.0, ws=None):
+    """dl fp32 [N,1,OD,OH,OW] -> dz 16-bit [N*D,H,W,Cin] (or None); dw [1,Cin,k,k,k] and db [1] += gscale * sums (or both None)."""
+    _f32(w, "w"); _f32(dl, "dl"); _f32(dw, "dw"); _f32(db, "db"); _f32(ws, "ws")
+    ref = x if x is not None else dz
+    _dev(ref)
+    N, D, H, W, Cin, OD, OH, OW = _head3d_shapes("conv3d_head_bwd", ref, w, dl, k, pad)
+    if dw is not None:
+        need = int(_lib.load().gs_conv3d_head_bwd_ws_floats(N, OD, OH, OW, Cin, k))
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.float32, device=ref.device)
+        elif ws.numel() < need:
+            raise ValueError("conv3d_head_bwd: ws needs gs_conv3d_head_bwd_ws_floats floats")
+    _head3d_call("gs_conv3d_head_bwd", Cin, k, pad, _p(x), _p(w), _p(dl), _p(dz), _p(dw), _p(db), _p(ws), N, D, H, W, Cin, OD, OH, OW,
+                 k, pad, float(gscale), dt_code(ref), _stream())
