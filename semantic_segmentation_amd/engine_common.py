@@ -1,5 +1,6 @@
-"""Host-side rules shared by the engines (unet_engine, block_engine, unet3d_engine, pix2pix_engine): the compute dtype, the
-reuse policy of the 16-bit weight packs, the owner cache of a network's parameters and the BatchNorm coefficient rule.  Nothing
+"""Host-side rules shared by the engines (unet_engine, block_engine, unet3d_engine, and the Pix2Pix plans pix2pix_engine, resnet_engine,
+discriminator_engine): the compute dtype, the reuse policy of the 16-bit weight packs, the owner cache of a network's parameters and
+the BatchNorm coefficient rule.  Nothing
 here launches a kernel of its own beyond what ops.bn_finalize / ops.bn_eval_coeffs do; it imports none of the engines."""
 from __future__ import annotations
 

@@ -5,7 +5,8 @@ Same public names, module tree and state-dict keys as the reference for the part
 `ResnetGenerator` (+ `ResnetBlock`), `NLayerDiscriminator`, `PixelDiscriminator`, `GANLoss`, `get_norm_layer`, `init_weights`, `init_net`, `define_G`, `define_D`, and the
 architecture tensors `upconv_arch` / `conv_arch` / `arch_parameters()` (module globals, :443,:477-484).
 The leaf torch modules only hold parameters; `UnetGenerator.forward` and `NLayerDiscriminator.forward`
-run whole-network plans on the HIP kernels (pix2pix_engine.py).  No ATen / CPU fallback."""
+run whole-network plans on the HIP kernels (pix2pix_engine.py: the U-Net generator and the steps all plans share; resnet_engine.py;
+discriminator_engine.py: the discriminators on images and on volumes).  No ATen / CPU fallback."""
 import functools
 
 import torch
@@ -347,7 +348,7 @@ class ResnetGenerator(nn.Module):
 class NLayerDiscriminator(nn.Module):
     """networks.py:620-665 PatchGAN (same Sequential indices: convs at 0,2,5,8,11; norms at 3,6,9).  With a 3-D norm layer
     (GenSeg-3D/models/networks.py:806-855) the leaves are nn.Conv3d -- same indices, 5-D weights -- and the plan is
-    pix2pix3d_engine.Discriminator3DEngine."""
+    discriminator_engine.Discriminator3DEngine."""
 
     def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, compute_dtype=None):
         super(NLayerDiscriminator, self).__init__()
@@ -368,10 +369,10 @@ class NLayerDiscriminator(nn.Module):
         self.model = nn.Sequential(*sequence)
         self.threed = threed
         if threed:
-            from .pix2pix3d_engine import Discriminator3DEngine
+            from .discriminator_engine import Discriminator3DEngine
             object.__setattr__(self, "_engine", Discriminator3DEngine(self, compute_dtype))
         else:
-            from .pix2pix_engine import DiscriminatorEngine
+            from .discriminator_engine import DiscriminatorEngine
             object.__setattr__(self, "_engine", DiscriminatorEngine(self, compute_dtype))
 
     @property
@@ -400,10 +401,10 @@ class PixelDiscriminator(nn.Module):
             conv_layer(ndf * 2, 1, kernel_size=1, stride=1, padding=0, bias=use_bias))
         self.threed = threed
         if threed:
-            from .pix2pix3d_engine import Discriminator3DEngine
+            from .discriminator_engine import Discriminator3DEngine
             object.__setattr__(self, "_engine", Discriminator3DEngine(self, compute_dtype, seq="net"))
         else:
-            from .pix2pix_engine import DiscriminatorEngine
+            from .discriminator_engine import DiscriminatorEngine
             object.__setattr__(self, "_engine", DiscriminatorEngine(self, compute_dtype, seq="net"))
 
     @property

@@ -9,15 +9,13 @@ Under InstanceNorm (a stage that saved `inorm`) gs_in_act_bwd takes the place of
 consumers; a bias directly in front of an InstanceNorm gets exact zeros (and no share in d arch), the other biases gs_colsum."""
 from __future__ import annotations
 
-import math
 import os
-from typing import Dict
 
 import torch
 
 from .. import ops
-from .._lib import ACT_LEAKY02, ACT_NONE, ACT_RELU, ACT_TANH
-from .pix2pix_engine import cached_geom, g_tapw_identity, image_conv_dgrad, image_conv_wgrad
+from .._lib import ACT_LEAKY02, ACT_RELU, ACT_TANH
+from .pix2pix_engine import cached_geom, conv_s2_dgrad, conv_wgrad, grad_scale, image_conv_dgrad, image_conv_wgrad, norm_act_bwd
 
 TAPS64 = tuple((ky - 3, kx - 3) for ky in range(8) for kx in range(8))
 
@@ -32,7 +30,7 @@ def generator_backward(engine, ctx, arch, dout, need_dx):
     R, L, levels, ups = ctx["R"], ctx["L"], ctx["levels"], ctx["ups"]
     dev = dout.device
     H, W = hs[0], ws[0]
-    S = float(2 ** round(math.log2(N * H * W)))
+    S = grad_scale(N * H * W)
     inv_s = 1.0 / S
     # (data parallel: every parameter gradient is announced to the reducer as soon as it is final -- parallel.GradEmitter)
     from ..parallel import GradEmitter
@@ -47,33 +45,13 @@ def generator_backward(engine, ctx, arch, dout, need_dx):
     def emit(p, g):
         emitter.emit(names[id(p)], g)
 
-    def bn_bwd(y, coef, stats, bnmod, dz_a, sa, ca, act, dz_b=None, act_b=ACT_NONE, keep=None, kscale=1.0, inorm=None):
-        """gradient w.r.t. the raw conv output y of  act(bn(y)) [two consumers / dropout]; emits dgamma/dbeta.
-        inorm: the (mean, invstd) [2,N,C] of an InstanceNorm stage (no parameters: nothing is emitted)."""
-        _, h, w, C = y.shape
-        dy = empty(N, h, w, C)
-        if inorm is not None:
-            ops.in_act_bwd(y, inorm[0], inorm[1], dz_a, sa, ca, act, dy, empty(2, N, C, dtype=torch.float32),
-                           ops.in_workspace(N, h, w, C, dev), dz_b=dz_b, act_b=act_b, keep_mask=keep, keep_scale=kscale)
-            return dy
-        if bnmod is None:
-            ops.bn_act_bwd_apply(y, dz_a, sa, ca, None, None, None, None, None, None, None, act, False, dy,
-                                 dz_b=dz_b, act_b=act_b, keep_mask=keep, keep_scale=kscale)
-            return dy
-        nt = ops.bn_bwd_tiles_used(N, h, w, False)
-        part = empty(ops.bn_partials_numel(ops.bn_bwd_tiles(N, h, w), C), dtype=torch.float32)
-        ops.bn_act_bwd_reduce(y, dz_a, sa, ca, None, coef[0], coef[1], coef[2], coef[3], act, part,
-                              dz_b=dz_b, act_b=act_b, keep_mask=keep, keep_scale=kscale)
-        dgamma = empty(C, dtype=torch.float32)
-        dbeta = empty(C, dtype=torch.float32)
-        c12 = empty(2, C, dtype=torch.float32)
-        ops.bn_bwd_coeffs(part, nt, C, N * h * w, inv_s, dgamma, dbeta, c12[0], c12[1])
-        if not stats:
-            c12.zero_()
-        ops.bn_act_bwd_apply(y, dz_a, sa, ca, None, coef[0], coef[1], coef[2], coef[3], c12[0], c12[1], act, True, dy,
-                             dz_b=dz_b, act_b=act_b, keep_mask=keep, keep_scale=kscale)
-        emit(bnmod.weight, dgamma)
-        emit(bnmod.bias, dbeta)
+    def bn_bwd(y, st, bnmod, dz_a, sa, ca, act, **kw):
+        """gradient w.r.t. the raw conv output y of  act(norm(y)) [two consumers / dropout] from the stage's saved state st (coef,
+        stats, and `inorm` under InstanceNorm); emits dgamma/dbeta of a BatchNorm"""
+        dy, dgamma, dbeta = norm_act_bwd(y, st["coef"], st.get("inorm"), st["stats"], dz_a, sa, ca, act, inv_s, N, **kw)
+        if dgamma is not None:
+            emit(bnmod.weight, dgamma)
+            emit(bnmod.bias, dbeta)
         return dy
 
     def bias_grad(conv, dy, cancelled):
@@ -164,8 +142,7 @@ def generator_backward(engine, ctx, arch, dout, need_dx):
         info = ups[d]
         upnorm = parts[d][3]
         src = dR_levels[d]                                        # [N,h_d,w_d,2c_d]; second half belongs to block d
-        du = bn_bwd(info["u"], info["coef"], info["stats"], upnorm, src, 2 * c[d], c[d], ACT_RELU,
-                    keep=info["keep"], kscale=info["kscale"], inorm=info.get("inorm"))
+        du = bn_bwd(info["u"], info, upnorm, src, 2 * c[d], c[d], ACT_RELU, keep=info["keep"], kscale=info["kscale"])
         dR_levels[d + 1] = upconv_bwd(d, du, info["cout"])
 
     # ---- down path, innermost first ------------------------------------------------------------------
@@ -176,10 +153,9 @@ def generator_backward(engine, ctx, arch, dout, need_dx):
         conv, downnorm = parts[k - 1][0], parts[k - 1][1]
         src = dR_levels[k]
         if k == D:                                                 # innermost: only the ReLU consumer
-            dy = bn_bwd(lv["y"], lv["coef"], lv["stats"], downnorm, src, c[k], 0, ACT_RELU)
+            dy = bn_bwd(lv["y"], lv, downnorm, src, c[k], 0, ACT_RELU)
         else:
-            dy = bn_bwd(lv["y"], lv["coef"], lv["stats"], downnorm, src, 2 * c[k], 0, ACT_RELU,
-                        dz_b=dL, act_b=ACT_LEAKY02, inorm=lv.get("inorm"))
+            dy = bn_bwd(lv["y"], lv, downnorm, src, 2 * c[k], 0, ACT_RELU, dz_b=dL, act_b=ACT_LEAKY02)
         bias_grad(conv, dy, lv.get("inorm") is not None)
         if k == 1:
             emit(conv.weight, image_conv_wgrad(ctx["x"], dy, conv, 4, 2, 1, inv_s))
@@ -187,14 +163,9 @@ def generator_backward(engine, ctx, arch, dout, need_dx):
                 dx = image_conv_dgrad(dy, conv, ctx["x"], 4, 2, 1, inv_s)
         else:
             cin, cout = c[k - 1], c[k]
-            # K parts in slabs + ordered reduction fused with scale / unpack (one part: a plain store): deterministic
-            dw = torch.empty_like(conv.weight, memory_format=torch.contiguous_format)
-            wsl = empty(ops.conv_wgrad_ws_floats(lv["geom"]), dtype=torch.float32)
-            ops.conv_wgrad_det(lv["geom"], lv["inp"], dy, wsl, dw, cout, cin, 16, inv_s)
-            emit(conv.weight, dw)
+            emit(conv.weight, conv_wgrad(lv["geom"], lv["inp"], dy, conv.weight, cout, cin, 16, inv_s))
             dL = empty(N, hs[k - 1], ws[k - 1], cin)
-            gds = [cached_geom(ops.geom_conv_s2_dgrad_class, N, hs[k - 1], ws[k - 1], cin, cout, 4, 1, cls >> 1, cls & 1) for cls in range(4)]
-            ops.conv_igemm_batch(gds, dy, [lv["wd"]] * 4, dL)
+            conv_s2_dgrad(dy, lv["wd"], dL, 4, 1)
     if getattr(engine, "after_backward", None) is not None:
         engine.after_backward()
     return grads, darch.to(arch.device), dx

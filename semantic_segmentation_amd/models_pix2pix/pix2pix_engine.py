@@ -1,4 +1,5 @@
-"""Whole-network plans of the Pix2Pix generator and PatchGAN discriminator on the HIP kernels.
+"""Whole-network plan of the Pix2Pix U-Net generator on the HIP kernels, and the steps every Pix2Pix plan shares (this generator,
+resnet_engine.py, and the discriminators of discriminator_engine.py -- the "Discriminator" notes below describe that plan on images).
 
 Generator (reference models_pix2pix/networks.py:514-617, 8 levels at 256x256):
   * every 4x4/stride-2 down-conv is one MFMA implicit GEMM (the 1-channel outermost one a direct kernel that
@@ -180,6 +181,107 @@ class _EmitDict:
 
 
 # =====================================================================================================
+# Steps every Pix2Pix plan shares (generator, ResNet generator, the discriminators of discriminator_engine.py)
+# =====================================================================================================
+def grad_scale(n):
+    """the power of two nearest to n: gradients are carried multiplied by it (see unet_engine.py)"""
+    return float(2 ** round(math.log2(n)))
+
+
+def pack_conv(w, tdt, transposed=False, view=None):
+    """(forward pack [taps][Cout][Cin], data-gradient pack [taps][Cin][Cout]) in the 16-bit dtype tdt of a conv weight
+    [Cout][Cin][kh][kw] (transposed: [Cin][Cout][kh][kw]).  view: what turns a weight of another rank into the 4-D tensor
+    gs_pack_weight takes (ops.conv3d_weight_view for [Cout][Cin][k][k][k])."""
+    w = w.detach().contiguous()
+    if view is not None:
+        w = view(w)
+    a, b, kh, kw = w.shape
+    cout, cin = (b, a) if transposed else (a, b)
+    wf = torch.empty((kh * kw, cout, cin), dtype=tdt, device=w.device)
+    wd = torch.empty((kh * kw, cin, cout), dtype=tdt, device=w.device)
+    ops.pack_weight(w, wf, wd, transposed)
+    return wf, wd
+
+
+def dropout_keep(drop, training, masks, i, N, h, w, C, dev):
+    """(uint8 keep-mask [N,h,w,C] or None, scale) of the Dropout module `drop`: masks[i] where the caller brought masks, else drawn
+    with torch.rand on the device"""
+    if drop is None or not training or not drop.p > 0:
+        return None, 1.0
+    if masks is not None:
+        keep = masks[i].to(dev).contiguous()
+    else:
+        keep = (torch.rand((N, h, w, C), device=dev) >= drop.p).to(torch.uint8)
+    return keep, 1.0 / (1.0 - drop.p)
+
+
+def per_sample(t, N):
+    """[N*D,H,W,C] -> the [N, D*H, W, C] view the per-sample norm kernels take (a volume is one plane of D*H rows; csrc/instnorm.hip
+    only uses H*W).  An image batch [N,H,W,C] is that view already and is returned as it is."""
+    ND, H, W, C = t.shape
+    return t if ND == N else t.view(N, (ND // N) * H, W, C)
+
+
+def norm_act_bwd(y, coef, inorm, stats, dz_a, sa, ca, act, inv_s, N, dz_b=None, act_b=ACT_NONE, keep=None, kscale=1.0):
+    """Gradient w.r.t. the stored conv output y [N*D,H,W,C] of  act(norm(y)) [two consumers dz_a/act and dz_b/act_b, dropout
+    keep * kscale] -> (dy, dgamma, dbeta); the last two are None unless the norm is a BatchNorm.
+    inorm: the (mean, invstd) [2,N,C] of an InstanceNorm stage (no parameters), taken per sample on the [N, D*H, W, C] view;
+    else coef: the [4,C] scale / shift / mean / invstd of a BatchNorm stage (engine_common.bn_coeffs), stats: whether they are
+    the batch's -- a stage that ran on running statistics has no gradient through mean and variance, so its c1 / c2 are zeros;
+    neither: no norm, the activation's gradient alone."""
+    nd, h, w, C = y.shape
+    dev = y.device
+    dy = torch.empty_like(y)
+    if inorm is not None:
+        yv = per_sample(y, N)
+        ops.in_act_bwd(yv, inorm[0], inorm[1], dz_a, sa, ca, act, dy, torch.empty((2, N, C), dtype=torch.float32, device=dev),
+                       ops.in_workspace(N, yv.shape[1], w, C, dev), dz_b=dz_b, act_b=act_b, keep_mask=keep, keep_scale=kscale)
+        return dy, None, None
+    if coef is None:
+        ops.bn_act_bwd_apply(y, dz_a, sa, ca, None, None, None, None, None, None, None, act, False, dy,
+                             dz_b=dz_b, act_b=act_b, keep_mask=keep, keep_scale=kscale)
+        return dy, None, None
+    nt = ops.bn_bwd_tiles_used(nd, h, w, False)
+    part = torch.empty(ops.bn_partials_numel(ops.bn_bwd_tiles(nd, h, w), C), dtype=torch.float32, device=dev)
+    ops.bn_act_bwd_reduce(y, dz_a, sa, ca, None, coef[0], coef[1], coef[2], coef[3], act, part,
+                          dz_b=dz_b, act_b=act_b, keep_mask=keep, keep_scale=kscale)
+    dgamma = torch.empty(C, dtype=torch.float32, device=dev)
+    dbeta = torch.empty(C, dtype=torch.float32, device=dev)
+    c12 = torch.empty((2, C), dtype=torch.float32, device=dev)
+    ops.bn_bwd_coeffs(part, nt, C, nd * h * w, inv_s, dgamma, dbeta, c12[0], c12[1])
+    if not stats:
+        c12.zero_()
+    ops.bn_act_bwd_apply(y, dz_a, sa, ca, None, coef[0], coef[1], coef[2], coef[3], c12[0], c12[1], act, True, dy,
+                         dz_b=dz_b, act_b=act_b, keep_mask=keep, keep_scale=kscale)
+    return dy, dgamma, dbeta
+
+
+def conv_wgrad(g, x, dy, w, A, B, taps, inv_s):
+    """weight gradient of the conv of geometry g straight into w's own layout [A][B][taps], from its input x and dy.
+    K parts in slabs + ordered reduction fused with scale / unpack (one part: a plain store): deterministic"""
+    dw = torch.empty_like(w, memory_format=torch.contiguous_format)
+    wsl = torch.empty(max(ops.conv_wgrad_ws_floats(g), 1), dtype=torch.float32, device=dy.device)
+    ops.conv_wgrad_det(g, x, dy, wsl, dw, A, B, taps, inv_s)
+    return dw
+
+
+def conv_s2_dgrad(dy, wd, dz, k, p):
+    """data gradient dz [N,IH,IW,Cin] of Conv2d(k, stride 2, padding p) from dy and the data-gradient pack wd: the four classes
+    of input pixels (row / column parity) in ONE launch"""
+    N, ih, iw, cin = dz.shape
+    gds = [cached_geom(ops.geom_conv_s2_dgrad_class, N, ih, iw, cin, dy.shape[3], k, p, cls >> 1, cls & 1) for cls in range(4)]
+    ops.conv_igemm_batch(gds, dy, [wd] * 4, dz)
+
+
+def param_grads(engine, grads, plist):
+    """what an autograd Function of these plans returns for the parameters plist (engine.param_list() at forward time) from the
+    gradients `grads` its backward emitted by state-dict name"""
+    fetch = engine.grad_fetch               # data parallel: the reduced gradients
+    return [(fetch(n) if (fetch is not None and n in grads) else grads.get(n)) if p.requires_grad else None
+            for n, p in zip(engine.param_names(), plist)]
+
+
+# =====================================================================================================
 # Generator
 # =====================================================================================================
 class GeneratorEngine(ParamIndex):
@@ -274,7 +376,7 @@ class GeneratorEngine(ParamIndex):
         for k in range(2, D + 1):
             conv, downnorm = parts[k - 1][0], parts[k - 1][1]
             wf, wd = self.packs.get(("down", k), _ver(conv.weight),
-                                    lambda conv=conv: self._pack_conv(conv.weight))
+                                    lambda conv=conv: pack_conv(conv.weight, tdt))
             g = cached_geom(ops.geom_conv, N, hs[k - 1], ws[k - 1], c[k - 1], c[k], 4, 2, 1)
             y = empty(N, hs[k], ws[k], c[k])
             if is_instance_norm(downnorm):                           # (never the innermost level: that one has no norm)
@@ -338,13 +440,7 @@ class GeneratorEngine(ParamIndex):
                     coef, stats, mi = None, True, instance_stats(u, upnorm)
                 else:
                     coef, stats = bn_coeffs(upnorm, part, 4 * mt, cout_t, N * H2 * W2, training, dev, nbt_pending)
-                keep, kscale = None, 1.0
-                if drop is not None and training and drop.p > 0:
-                    if dropout_masks is not None:
-                        keep = dropout_masks[mask_i].to(dev).contiguous()
-                    else:
-                        keep = (torch.rand((N, H2, W2, cout_t), device=dev) >= drop.p).to(torch.uint8)
-                    kscale = 1.0 / (1.0 - drop.p)
+                keep, kscale = dropout_keep(drop, training, dropout_masks, mask_i, N, H2, W2, cout_t, dev)
                 if drop is not None:
                     mask_i += 1
                 if inorm:
@@ -377,13 +473,6 @@ class GeneratorEngine(ParamIndex):
         ctx["R"], ctx["L"] = R, L
         _flush_nbt(nbt_pending)
         return out, (ctx if need_grad else None)
-
-    def _pack_conv(self, w):
-        cout, cin, kh, kw = w.shape
-        wf = torch.empty((kh * kw, cout, cin), dtype=self.tdt, device=w.device)
-        wd = torch.empty((kh * kw, cin, cout), dtype=self.tdt, device=w.device)
-        ops.pack_weight(w.detach().contiguous(), wf, wd, False)
-        return wf, wd
 
     def refresh_arch_packs(self, arch):
         """After an EAGER update of the architecture tensor while hipGraphs hold merged forward packs (harness.EndToEndTrainer):
@@ -453,240 +542,4 @@ class _GeneratorFunction(torch.autograd.Function):
             raise RuntimeError("UnetGenerator forward ran without gradient tracking")
         from .pix2pix_backward import generator_backward
         grads, darch, dx = generator_backward(ctx.engine, ctx.ectx, ctx.arch, dout, ctx.x_needs_grad)
-        names = ctx.engine.param_names()
-        fetch = ctx.engine.grad_fetch               # data parallel: the reduced gradients
-        out = [(fetch(n) if (fetch is not None and n in grads) else grads.get(n)) if p.requires_grad else None
-               for n, p in zip(names, ctx.plist)]
-        return (None, None, None, None, dx, darch, *out)
-
-
-# =====================================================================================================
-# Discriminator
-# =====================================================================================================
-class DiscriminatorEngine(ParamIndex):
-    def __init__(self, net, dtype=None, seq="model"):
-        """seq: the attribute of `net` that holds the reference's Sequential: `model` (NLayerDiscriminator, networks.py:661) or
-        `net` (PixelDiscriminator, :693 -- the same conv / norm / LeakyReLU stages with 1x1 kernels, so the same plan)"""
-        self.net = net
-        self.seq = seq
-        self.dtype, self.tdt = compute_dtype(dtype)
-        self.packs = _PackCache()
-        self.trust_versions = False      # see engine_common.pack_reuse_allowed
-        self.grad_ready_hook = self.after_backward = self.grad_fetch = None      # parallel.GradReducer.attach
-
-    def run(self, x):
-        params = self.param_list()
-        need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-        return _DiscriminatorFunction.apply(self, self.net.training, need_grad, x, *params)
-
-    def layout(self):
-        seq = list(getattr(self.net, self.seq))
-        convs = [(i, m) for i, m in enumerate(seq) if isinstance(m, torch.nn.Conv2d)]
-        stages = []
-        for idx, (i, conv) in enumerate(convs):
-            bn = seq[i + 1] if i + 1 < len(seq) and isinstance(seq[i + 1], (torch.nn.BatchNorm2d, torch.nn.InstanceNorm2d)) else None
-            stages.append((i, conv, bn))
-        return stages
-
-    def forward(self, x, training, need_grad):
-        stages = self.layout()
-        if x.dim() != 4:
-            raise ValueError(f"a 2-D discriminator takes an image batch [N,C,H,W], got a {x.dim()}-D tensor {tuple(x.shape)} "
-                             "(volumes: define_D(..., threed=True))")
-        _check_image_conv("discriminator", x.shape[1], stages[0][1].out_channels)
-        _need_cuda(x)
-        tdt = self.tdt
-        dev = x.device
-        x = x.contiguous().float()
-        N, cin0, H, W = x.shape
-        sq = self.seq
-        if not pack_reuse_allowed(need_grad, self.trust_versions):
-            self.packs.clear()       # training forwards always re-pack: `.data` writes (Betty) bump no version counter
-
-        def empty(*shape, dtype=tdt):
-            return torch.empty(shape, dtype=dtype, device=dev)
-
-        # InstanceNorm needs planes of more than one element (16 x 16 through three layers ends at 1 x 1): refused before any launch
-        ch, cw = H, W
-        for (i, conv, bn) in stages[:-1]:
-            ch = ops.conv_out_size(ch, conv.kernel_size[0], conv.stride[0], conv.padding[0])
-            cw = ops.conv_out_size(cw, conv.kernel_size[0], conv.stride[0], conv.padding[0])
-            if is_instance_norm(bn) and ch * cw < 2:
-                raise ValueError(f"Expected more than 1 spatial element when training, got input size "
-                                 f"{[N, conv.out_channels, ch, cw]} (InstanceNorm2d {sq}.{i + 1})")
-        recs = []
-        nbt_pending = []
-        # stage 0: direct conv + bias + LeakyReLU (no norm)
-        i0, conv0, _ = stages[0]
-        k, s, p = conv0.kernel_size[0], conv0.stride[0], conv0.padding[0]
-        h, w = ops.conv_out_size(H, k, s, p), ops.conv_out_size(W, k, s, p)
-        z = empty(N, h, w, conv0.out_channels)
-        image_conv_fwd(x, conv0, z, k, s, p, ACT_LEAKY02)
-        recs.append(dict(kind="first", conv=conv0, x=x, z=z, k=k, s=s, p=p, name=f"{sq}.{i0}"))
-        cur, ch, cw, cc = z, h, w, conv0.out_channels
-        for (i, conv, bn) in stages[1:-1]:
-            k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-            inorm = is_instance_norm(bn)
-            if bn is None or (conv.bias is not None and not inorm):
-                raise NotImplementedError("PatchGAN middle convs are expected as conv(no bias) -> BatchNorm -> LeakyReLU or "
-                                          "conv -> InstanceNorm -> LeakyReLU")
-            wf, wd = self.packs.get(("conv", i), _ver(conv.weight), lambda conv=conv: self._pack(conv.weight))
-            g = cached_geom(ops.geom_conv, N, ch, cw, cc, conv.out_channels, k, s, p)
-            oh, ow = g.OH, g.OW
-            y = empty(N, oh, ow, conv.out_channels)
-            z = empty(N, oh, ow, conv.out_channels)
-            if inorm:
-                ops.conv_igemm(g, cur, wf, y, None, None)            # the conv's bias cancels in the norm: not added
-                mi = instance_stats(y, bn)
-                ops.in_act_apply(y, mi[0], mi[1], ACT_LEAKY02, z, conv.out_channels, 0)
-                recs.append(dict(kind="mid", conv=conv, bn=bn, inp=cur, y=y, coef=None, stats=True, inorm=mi, geom=g, wd=wd,
-                                 k=k, s=s, p=p, ih=ch, iw=cw, cin=cc, name=f"{sq}.{i}", bnname=f"{sq}.{i + 1}"))
-                cur, ch, cw, cc = z, oh, ow, conv.out_channels
-                continue
-            mt = ops.conv_igemm_mtiles(g)
-            use_stats = training or bn.running_mean is None
-            part = empty(ops.bn_partials_numel(mt, conv.out_channels), dtype=torch.float32) if use_stats else None
-            ops.conv_igemm(g, cur, wf, y, None, part)
-            coef, stats = bn_coeffs(bn, part, mt, conv.out_channels, N * oh * ow, training, dev, nbt_pending)
-            ops.bn_act_apply(y, coef[0], coef[1], ACT_LEAKY02, z, conv.out_channels, 0)
-            recs.append(dict(kind="mid", conv=conv, bn=bn, inp=cur, y=y, coef=coef, stats=stats, geom=g, wd=wd,
-                             k=k, s=s, p=p, ih=ch, iw=cw, cin=cc, name=f"{sq}.{i}", bnname=f"{sq}.{i + 1}"))
-            cur, ch, cw, cc = z, oh, ow, conv.out_channels
-        il, convl, _ = stages[-1]
-        k, s, p = convl.kernel_size[0], convl.stride[0], convl.padding[0]
-        oh, ow = ops.conv_out_size(ch, k, s, p), ops.conv_out_size(cw, k, s, p)
-        logits = torch.empty((N, convl.out_channels, oh, ow), dtype=torch.float32, device=dev)
-        ops.conv_smallcout_fwd(cur, convl.weight.detach().contiguous(),
-                               convl.bias.detach() if convl.bias is not None else None, logits, k, s, p)
-        recs.append(dict(kind="last", conv=convl, inp=cur, k=k, s=s, p=p, ih=ch, iw=cw, cin=cc, name=f"{sq}.{il}"))
-        _flush_nbt(nbt_pending)
-        return logits, (dict(recs=recs, N=N, H=H, W=W) if need_grad else None)
-
-    def _pack(self, w):
-        cout, cin, kh, kw = w.shape
-        wf = torch.empty((kh * kw, cout, cin), dtype=self.tdt, device=w.device)
-        wd = torch.empty((kh * kw, cin, cout), dtype=self.tdt, device=w.device)
-        ops.pack_weight(w.detach().contiguous(), wf, wd, False)
-        return wf, wd
-
-    @staticmethod
-    def _mid_conv_bwd(rec, dy, grads, inv_s, empty):
-        """weight gradient (emitted) and data gradient (returned) of a middle conv from dy: the launches of backward() below"""
-        conv = rec["conv"]
-        N, _, _, cout = dy.shape
-        k, s, p, cin = rec["k"], rec["s"], rec["p"], rec["cin"]
-        dw = torch.empty_like(conv.weight, memory_format=torch.contiguous_format)
-        wsl = empty(ops.conv_wgrad_ws_floats(rec["geom"]), dtype=torch.float32)
-        ops.conv_wgrad_det(rec["geom"], rec["inp"], dy, wsl, dw, cout, cin, k * k, inv_s)
-        grads[rec["name"] + ".weight"] = dw
-        dz = empty(N, rec["ih"], rec["iw"], cin)
-        if s == 1:
-            ops.conv_igemm(cached_geom(ops.geom_conv_dgrad_s1, N, rec["ih"], rec["iw"], cin, cout, k, p), dy, rec["wd"], dz)
-        else:
-            gds = [cached_geom(ops.geom_conv_s2_dgrad_class, N, rec["ih"], rec["iw"], cin, cout, k, p, cls >> 1, cls & 1)
-                   for cls in range(4)]
-            ops.conv_igemm_batch(gds, dy, [rec["wd"]] * 4, dz)
-        return dz
-
-    def backward(self, ctx, dlogits, need_dx):
-        tdt = self.tdt
-        recs, N = ctx["recs"], ctx["N"]
-        dev = dlogits.device
-        S = float(2 ** round(math.log2(max(dlogits.numel(), 1))))
-        inv_s = 1.0 / S
-        from ..parallel import GradEmitter
-        emitter = GradEmitter(self.grad_ready_hook)          # data parallel: announced as soon as final
-        grads = _EmitDict(emitter)
-
-        def empty(*shape, dtype=tdt):
-            return torch.empty(shape, dtype=dtype, device=dev)
-
-        last = recs[-1]
-        conv = last["conv"]
-        dl = dlogits.contiguous().float() * S
-        dw = torch.zeros_like(conv.weight, memory_format=torch.contiguous_format)
-        db = torch.zeros_like(conv.bias) if conv.bias is not None else None
-        dz = empty(*last["inp"].shape)
-        ops.conv_smallcout_bwd(last["inp"], conv.weight.detach().contiguous(), dl, dz, dw, db,
-                               last["k"], last["s"], last["p"], inv_s)
-        grads[last["name"] + ".weight"] = dw
-        if db is not None:
-            grads[last["name"] + ".bias"] = db
-        for rec in reversed(recs[1:-1]):
-            conv, coef = rec["conv"], rec["coef"]
-            y = rec["y"]
-            _, oh, ow, cout = y.shape
-            inorm = rec.get("inorm")
-            if inorm is not None:
-                dy = empty(N, oh, ow, cout)
-                ops.in_act_bwd(y, inorm[0], inorm[1], dz, cout, 0, ACT_LEAKY02, dy, empty(2, N, cout, dtype=torch.float32),
-                               ops.in_workspace(N, oh, ow, cout, dev))
-                dz = self._mid_conv_bwd(rec, dy, grads, inv_s, empty)
-                if conv.bias is not None:                            # cancelled by the norm: exact zeros
-                    grads[rec["name"] + ".bias"] = torch.zeros_like(conv.bias)
-                continue
-            nt = ops.bn_bwd_tiles_used(N, oh, ow, False)
-            part = empty(ops.bn_partials_numel(ops.bn_bwd_tiles(N, oh, ow), cout), dtype=torch.float32)
-            ops.bn_act_bwd_reduce(y, dz, cout, 0, None, coef[0], coef[1], coef[2], coef[3], ACT_LEAKY02, part)
-            dgamma = empty(cout, dtype=torch.float32)
-            dbeta = empty(cout, dtype=torch.float32)
-            c12 = empty(2, cout, dtype=torch.float32)
-            ops.bn_bwd_coeffs(part, nt, cout, N * oh * ow, inv_s, dgamma, dbeta, c12[0], c12[1])
-            if not rec["stats"]:
-                c12.zero_()
-            dy = empty(N, oh, ow, cout)
-            ops.bn_act_bwd_apply(y, dz, cout, 0, None, coef[0], coef[1], coef[2], coef[3], c12[0], c12[1],
-                                 ACT_LEAKY02, True, dy)
-            k, s, p, cin = rec["k"], rec["s"], rec["p"], rec["cin"]
-            # K parts in slabs + ordered reduction fused with scale / unpack (one part: a plain store): deterministic
-            dw = torch.empty_like(conv.weight, memory_format=torch.contiguous_format)
-            wsl = empty(ops.conv_wgrad_ws_floats(rec["geom"]), dtype=torch.float32)
-            ops.conv_wgrad_det(rec["geom"], rec["inp"], dy, wsl, dw, cout, cin, k * k, inv_s)
-            grads[rec["name"] + ".weight"] = dw
-            grads[rec["bnname"] + ".weight"] = dgamma
-            grads[rec["bnname"] + ".bias"] = dbeta
-            dz = empty(N, rec["ih"], rec["iw"], cin)
-            if s == 1:
-                ops.conv_igemm(cached_geom(ops.geom_conv_dgrad_s1, N, rec["ih"], rec["iw"], cin, cout, k, p), dy, rec["wd"], dz)
-            else:
-                gds = [cached_geom(ops.geom_conv_s2_dgrad_class, N, rec["ih"], rec["iw"], cin, cout, k, p, cls >> 1, cls & 1)
-                       for cls in range(4)]
-                ops.conv_igemm_batch(gds, dy, [rec["wd"]] * 4, dz)
-        first = recs[0]
-        conv = first["conv"]
-        z = first["z"]
-        dy = empty(*z.shape)
-        # z = leaky(conv + bias): the activation gradient only needs the sign, which z preserves
-        ops.bn_act_bwd_apply(z, dz, z.shape[3], 0, None, None, None, None, None, None, None, ACT_LEAKY02, False, dy)
-        grads[first["name"] + ".weight"] = image_conv_wgrad(first["x"], dy, conv, first["k"], first["s"], first["p"], inv_s)
-        if conv.bias is not None:
-            ws = empty(1024 * z.shape[3], dtype=torch.float32)
-            db = empty(z.shape[3], dtype=torch.float32)
-            ops.colsum(dy, z.shape[3], 0, N, z.shape[1], z.shape[2], 0, 0, z.shape[1], z.shape[2], z.shape[3], inv_s, ws, db)
-            grads[first["name"] + ".bias"] = db
-        dx = None
-        if need_dx:
-            dx = image_conv_dgrad(dy, conv, first["x"], first["k"], first["s"], first["p"], inv_s)
-        if self.after_backward is not None:
-            self.after_backward()
-        return emitter.grads, dx
-
-
-class _DiscriminatorFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, engine, training, need_grad, x, *plist):
-        logits, ectx = engine.forward(x, training, need_grad)
-        ctx.engine, ctx.ectx, ctx.plist = engine, ectx, plist
-        ctx.x_needs_grad = x.requires_grad
-        return logits
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        if ctx.ectx is None:
-            raise RuntimeError("NLayerDiscriminator forward ran without gradient tracking")
-        grads, dx = ctx.engine.backward(ctx.ectx, dlogits, ctx.x_needs_grad)
-        names = ctx.engine.param_names()
-        fetch = ctx.engine.grad_fetch               # data parallel: the reduced gradients
-        out = [(fetch(n) if (fetch is not None and n in grads) else grads.get(n)) if p.requires_grad else None
-               for n, p in zip(names, ctx.plist)]
-        return (None, None, None, dx, *out)
+        return (None, None, None, None, dx, darch, *param_grads(ctx.engine, grads, ctx.plist))

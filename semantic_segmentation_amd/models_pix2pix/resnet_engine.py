@@ -19,14 +19,13 @@ runs give equal bits.  Gradients are carried multiplied by a power-of-two scale 
 A conv bias directly in front of an InstanceNorm cancels: it is not added and its gradient is exact zeros (pix2pix_engine.py)."""
 from __future__ import annotations
 
-import math
-
 import torch
 
 from .. import ops
 from .._lib import ACT_NONE, ACT_RELU
 from ..engine_common import ParamIndex, _flush_nbt, bn_coeffs, compute_dtype, pack_reuse_allowed
-from .pix2pix_engine import _PackCache, _need_cuda, _ver, cached_geom, instance_stats, is_instance_norm
+from .pix2pix_engine import (_PackCache, _need_cuda, _ver, cached_geom, conv_s2_dgrad, conv_wgrad, dropout_keep, grad_scale,
+                             instance_stats, is_instance_norm, norm_act_bwd, pack_conv, param_grads)
 
 PAD_MSG = "Padding size should be less than the corresponding input dimension"
 
@@ -79,16 +78,8 @@ class ResnetGeneratorEngine(ParamIndex):
         need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
         return _ResnetGeneratorFunction.apply(self, self.net.training, need_grad, dropout_masks, x, *params)
 
-    def _pack(self, w, transposed):
-        a, b, kh, kw = w.shape
-        cout, cin = (b, a) if transposed else (a, b)
-        wf = torch.empty((kh * kw, cout, cin), dtype=self.tdt, device=w.device)
-        wd = torch.empty((kh * kw, cin, cout), dtype=self.tdt, device=w.device)
-        ops.pack_weight(w.detach().contiguous(), wf, wd, transposed)
-        return wf, wd
-
     def _packs_of(self, name, conv, transposed=False):
-        return self.packs.get(("conv", name), _ver(conv.weight), lambda: self._pack(conv.weight, transposed))
+        return self.packs.get(("conv", name), _ver(conv.weight), lambda: pack_conv(conv.weight, self.tdt, transposed))
 
     def invalidate_packs(self):
         self.packs.clear()
@@ -179,13 +170,7 @@ class ResnetGeneratorEngine(ParamIndex):
             part = partials(norm1, mt3, C)
             ops.conv_igemm(g3, P, wf1, y1, None, part)
             n1 = coefs(norm1, y1, part, mt3)
-            keep, kscale = None, 1.0
-            if drop is not None and training and drop.p > 0:
-                if dropout_masks is not None:
-                    keep = dropout_masks[b].to(dev).contiguous()
-                else:
-                    keep = (torch.rand((N, h, w, C), device=dev) >= drop.p).to(torch.uint8)
-                kscale = 1.0 / (1.0 - drop.p)
+            keep, kscale = dropout_keep(drop, training, dropout_masks, b, N, h, w, C, dev)
             Q = apply(n1, y1, ACT_RELU, 1, keep=keep, kscale=kscale)
             y2 = empty(N, h, w, C)
             part = partials(norm2, mt3, C)
@@ -227,7 +212,7 @@ def resnet_generator_backward(engine, ctx, dout, need_dx):
     tdt = engine.tdt
     N, H, W = ctx["N"], ctx["H"], ctx["W"]
     dev = dout.device
-    S = float(2 ** round(math.log2(N * H * W)))
+    S = grad_scale(N * H * W)
     inv_s = 1.0 / S
     from ..parallel import GradEmitter
     emitter = GradEmitter(getattr(engine, "grad_ready_hook", None))     # data parallel: announced as soon as final
@@ -240,27 +225,11 @@ def resnet_generator_backward(engine, ctx, dout, need_dx):
 
     def norm_bwd(y, nc, name, dz, act, keep=None, kscale=1.0):
         """gradient w.r.t. the conv output y of act(norm(y)) [* keep]; emits the BatchNorm parameters' gradients under `name`"""
-        n, h, w, C = y.shape
-        dy = empty(n, h, w, C)
-        if nc["inorm"] is not None:
-            mi = nc["inorm"]
-            ops.in_act_bwd(y, mi[0], mi[1], dz, C, 0, act, dy, empty(2, n, C, dtype=torch.float32),
-                           ops.in_workspace(n, h, w, C, dev), keep_mask=keep, keep_scale=kscale)
-            return dy
-        coef = nc["coef"]
-        nt = ops.bn_bwd_tiles_used(n, h, w, False)
-        part = empty(ops.bn_partials_numel(ops.bn_bwd_tiles(n, h, w), C), dtype=torch.float32)
-        ops.bn_act_bwd_reduce(y, dz, C, 0, None, coef[0], coef[1], coef[2], coef[3], act, part, keep_mask=keep, keep_scale=kscale)
-        dgamma = empty(C, dtype=torch.float32)
-        dbeta = empty(C, dtype=torch.float32)
-        c12 = empty(2, C, dtype=torch.float32)
-        ops.bn_bwd_coeffs(part, nt, C, n * h * w, inv_s, dgamma, dbeta, c12[0], c12[1])
-        if not nc["stats"]:
-            c12.zero_()
-        ops.bn_act_bwd_apply(y, dz, C, 0, None, coef[0], coef[1], coef[2], coef[3], c12[0], c12[1], act, True, dy,
-                             keep_mask=keep, keep_scale=kscale)
-        emit(name + ".weight", dgamma)
-        emit(name + ".bias", dbeta)
+        dy, dgamma, dbeta = norm_act_bwd(y, nc["coef"], nc["inorm"], nc["stats"], dz, y.shape[3], 0, act, inv_s, N,
+                                         keep=keep, kscale=kscale)
+        if dgamma is not None:
+            emit(name + ".weight", dgamma)
+            emit(name + ".bias", dbeta)
         return dy
 
     def cancelled_bias(name, conv):
@@ -268,10 +237,7 @@ def resnet_generator_backward(engine, ctx, dout, need_dx):
             emit(name + ".bias", torch.zeros_like(conv.bias))
 
     def wgrad(g, x, dy, name, conv, A, B):
-        dw = torch.empty_like(conv.weight, memory_format=torch.contiguous_format)
-        wsl = empty(ops.conv_wgrad_ws_floats(g), dtype=torch.float32)
-        ops.conv_wgrad_det(g, x, dy, wsl, dw, A, B, 9, inv_s)
-        emit(name + ".weight", dw)
+        emit(name + ".weight", conv_wgrad(g, x, dy, conv.weight, A, B, 9, inv_s))
 
     def seq_name(name, off):
         head, _, idx = name.rpartition(".")
@@ -335,9 +301,7 @@ def resnet_generator_backward(engine, ctx, dout, need_dx):
         wgrad(rec["geom"], rec["inp"], dy, rec["name"], conv, cout, cin)
         cancelled_bias(rec["name"], conv)
         dz = empty(N, rec["ih"], rec["iw"], cin)
-        gds = [cached_geom(ops.geom_conv_s2_dgrad_class, N, rec["ih"], rec["iw"], cin, cout, 3, 1, cls >> 1, cls & 1)
-               for cls in range(4)]
-        ops.conv_igemm_batch(gds, dy, [rec["wd"]] * 4, dz)
+        conv_s2_dgrad(dy, rec["wd"], dz, 3, 1)
     # ---- stem ----------------------------------------------------------------------------------------------
     st = ctx["stem"]
     conv = st["conv"]
@@ -373,8 +337,4 @@ class _ResnetGeneratorFunction(torch.autograd.Function):
             raise RuntimeError("ResnetGenerator forward ran without gradient tracking")
         ctx.saved_tensors                           # (raises if the image was modified in place)
         grads, dx = resnet_generator_backward(ctx.engine, ctx.ectx, dout, ctx.x_needs_grad)
-        names = ctx.engine.param_names()
-        fetch = ctx.engine.grad_fetch               # data parallel: the reduced gradients
-        out = [(fetch(n) if (fetch is not None and n in grads) else grads.get(n)) if p.requires_grad else None
-               for n, p in zip(names, ctx.plist)]
-        return (None, None, None, None, dx, *out)
+        return (None, None, None, None, dx, *param_grads(ctx.engine, grads, ctx.plist))

@@ -1,7 +1,7 @@
 """fp64 replay of the Pix2Pix engines' backward plans from the state their forward saved.
 
 `generator_backward(engine, ctx, arch, dout, need_dx)` (models_pix2pix/pix2pix_backward.py) and `DiscriminatorEngine.backward(ctx,
-dlogits, need_dx)` (pix2pix_engine.py) are pure functions of `ctx` and the incoming gradient, and linear in it.  This module
+dlogits, need_dx)` (discriminator_engine.py) are pure functions of `ctx` and the incoming gradient, and linear in it.  This module
 restates both on the CPU in torch fp64, in the order of those functions, from a PLAIN state (NCHW fp64 tensors: no NHWC, no concat
 offsets, no padded image channels, no uint8 masks), as backward_replay.py does for the U-Net engines, and is held with that
 module's compare().

@@ -172,6 +172,90 @@ def test_pix2pix_version_keys_follow_pack_key(monkeypatch):
     assert pix2pix_engine._ver(a) != pix2pix_engine._ver(a)
 
 
+def test_pix2pix_norm_act_bwd_launch_sequence(monkeypatch):
+    """The one norm + activation backward of the Pix2Pix plans (pix2pix_engine.norm_act_bwd), on recording fakes: BatchNorm is
+    reduce -> coeffs -> apply with c1 / c2 all zeros where the stage ran on running statistics, InstanceNorm one gs_in_act_bwd
+    and no parameter gradients, no norm the apply pass alone."""
+    from semantic_segmentation_amd._lib import ACT_LEAKY02, ACT_NONE, ACT_RELU
+    from semantic_segmentation_amd.models_pix2pix import pix2pix_engine as pe
+    rec = []
+
+    def bn_act_bwd_reduce(y, dz_a, sa, ca, dzp, scale, shift, mean, invstd, act, partials, **kw):
+        rec.append(dict(kind="reduce", y=y, dz_a=dz_a, sa=sa, ca=ca, coef=(scale, shift, mean, invstd), act=act, partials=partials, kw=kw))
+
+    def bn_bwd_coeffs(partials, ntiles, C, count, gscale, dgamma, dbeta, c1, c2):
+        c1.fill_(3.0), c2.fill_(5.0)                      # (what the apply pass must not see after a stage on running statistics)
+        rec.append(dict(kind="coeffs", partials=partials, ntiles=ntiles, C=C, count=count, gscale=gscale, dgamma=dgamma, dbeta=dbeta))
+
+    def bn_act_bwd_apply(y, dz_a, sa, ca, dzp, scale, shift, mean, invstd, c1, c2, act, bn, dy, **kw):
+        rec.append(dict(kind="apply", y=y, dz_a=dz_a, sa=sa, ca=ca, coef=(scale, shift, mean, invstd), bn=bn, dy=dy, act=act, kw=kw,
+                        c1=None if c1 is None else c1.clone(), c2=None if c2 is None else c2.clone()))
+
+    def in_act_bwd(y, mean, invstd, dz_a, sa, ca, act, dy, gmeans, ws=None, **kw):
+        rec.append(dict(kind="in", y=y, mean=mean, invstd=invstd, dz_a=dz_a, sa=sa, ca=ca, act=act, dy=dy, gmeans=gmeans, ws=ws, kw=kw))
+    for f in (bn_act_bwd_reduce, bn_bwd_coeffs, bn_act_bwd_apply, in_act_bwd):
+        monkeypatch.setattr(pe.ops, f.__name__, f)
+    monkeypatch.setattr(pe.ops, "bn_bwd_tiles", lambda N, H, W: 6)
+    monkeypatch.setattr(pe.ops, "bn_bwd_tiles_used", lambda N, H, W, pooled: 5)
+    monkeypatch.setattr(pe.ops, "bn_partials_numel", lambda ntiles, C: 2 * ntiles * C)
+    monkeypatch.setattr(pe.ops, "in_workspace", lambda N, H, W, C, dev: ("ws", N, H, W, C))
+
+    N, H, W, C = 2, 3, 4, 8
+    y = torch.zeros((N, H, W, C), dtype=torch.float16)
+    dz, dzb = torch.zeros((N, H, W, 2 * C), dtype=torch.float16), torch.zeros_like(y)
+    coef = torch.zeros((4, C))
+    keep = torch.ones((N, H, W, C), dtype=torch.uint8)
+    kw = dict(dz_b=dzb, act_b=ACT_LEAKY02, keep_mask=keep, keep_scale=2.0)
+
+    def is_dy(t):
+        return t.shape == y.shape and t.dtype == y.dtype and t.is_contiguous()
+
+    # BatchNorm on batch statistics, with both consumers and a keep-mask: every launch sees them
+    dy, dgamma, dbeta = pe.norm_act_bwd(y, coef, None, True, dz, 2 * C, C, ACT_RELU, 0.25, N, dz_b=dzb, act_b=ACT_LEAKY02, keep=keep, kscale=2.0)
+    assert [r["kind"] for r in rec] == ["reduce", "coeffs", "apply"]
+    red, co, ap = rec
+    for r in (red, ap):
+        assert r["y"] is y and r["dz_a"] is dz and (r["sa"], r["ca"], r["act"]) == (2 * C, C, ACT_RELU) and r["kw"] == kw
+        assert all(a.data_ptr() == coef[i].data_ptr() for i, a in enumerate(r["coef"]))
+    assert red["partials"] is co["partials"] and red["partials"].numel() == 2 * 6 * C and red["partials"].dtype == torch.float32
+    assert (co["ntiles"], co["C"], co["count"], co["gscale"]) == (5, C, N * H * W, 0.25)
+    assert co["dgamma"] is dgamma and co["dbeta"] is dbeta and dgamma.shape == dbeta.shape == (C,) and dgamma.dtype == torch.float32
+    assert ap["bn"] is True and ap["dy"] is dy and is_dy(dy)
+    assert torch.equal(ap["c1"], torch.full((C,), 3.0)) and torch.equal(ap["c2"], torch.full((C,), 5.0))
+
+    # BatchNorm on running statistics: the same three launches, c1 / c2 all zeros
+    rec.clear()
+    dy, dgamma, dbeta = pe.norm_act_bwd(y, coef, None, False, dz, 2 * C, 0, ACT_LEAKY02, 0.25, N)
+    assert [r["kind"] for r in rec] == ["reduce", "coeffs", "apply"]
+    assert rec[2]["bn"] is True and rec[2]["dy"] is dy and rec[1]["dgamma"] is dgamma and rec[1]["dbeta"] is dbeta
+    assert rec[2]["c1"].shape == rec[2]["c2"].shape == (C,) and not rec[2]["c1"].any() and not rec[2]["c2"].any()
+    assert rec[0]["kw"] == rec[2]["kw"] == dict(dz_b=None, act_b=ACT_NONE, keep_mask=None, keep_scale=1.0)
+
+    # InstanceNorm: one launch on the per-sample view (an image batch: the tensor itself), nothing for gamma / beta
+    rec.clear()
+    mi = torch.zeros((2, N, C))
+    dy, dgamma, dbeta = pe.norm_act_bwd(y, None, mi, True, dz, 2 * C, C, ACT_RELU, 0.25, N, dz_b=dzb, act_b=ACT_LEAKY02, keep=keep, kscale=2.0)
+    (r,) = rec
+    assert r["kind"] == "in" and r["y"] is y and r["dz_a"] is dz and (r["sa"], r["ca"], r["act"]) == (2 * C, C, ACT_RELU) and r["kw"] == kw
+    assert r["mean"].data_ptr() == mi[0].data_ptr() and r["invstd"].data_ptr() == mi[1].data_ptr()
+    assert r["gmeans"].shape == (2, N, C) and r["gmeans"].dtype == torch.float32 and r["ws"] == ("ws", N, H, W, C)
+    assert r["dy"] is dy and is_dy(dy) and dgamma is None and dbeta is None
+    # ... a volume stored as depth slices [N*D,H,W,C] goes in as [N, D*H, W, C]; dy keeps the slices' shape
+    rec.clear()
+    dy, _, _ = pe.norm_act_bwd(y, None, mi[:, :1], True, dzb, C, 0, ACT_RELU, 0.25, 1)
+    (r,) = rec
+    assert r["y"].shape == (1, N * H, W, C) and r["y"].data_ptr() == y.data_ptr() and r["ws"] == ("ws", 1, N * H, W, C)
+    assert r["gmeans"].shape == (2, 1, C) and r["dy"] is dy and is_dy(dy)
+
+    # no norm: the apply pass alone, without coefficients
+    rec.clear()
+    dy, dgamma, dbeta = pe.norm_act_bwd(y, None, None, False, dzb, C, 0, ACT_LEAKY02, 0.25, N)
+    (r,) = rec
+    assert r["kind"] == "apply" and r["bn"] is False and r["coef"] == (None,) * 4 and r["c1"] is None and r["c2"] is None
+    assert r["y"] is y and r["dz_a"] is dzb and (r["sa"], r["ca"], r["act"]) == (C, 0, ACT_LEAKY02)
+    assert r["dy"] is dy and is_dy(dy) and dgamma is None and dbeta is None
+
+
 def test_compute_dtype(monkeypatch):
     monkeypatch.delenv("GSSEG_DTYPE", raising=False)
     assert ec.compute_dtype() == ("f16", torch.float16) == ec.compute_dtype("f16") == ec.compute_dtype("")

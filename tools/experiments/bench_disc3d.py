@@ -1,4 +1,4 @@
-"""The 3-D Pix2Pix discriminators (models_pix2pix/pix2pix3d_engine.py, csrc/ends3d.hip) timed at the reference's --crop_size, 64^3
+"""The 3-D Pix2Pix discriminators (models_pix2pix/discriminator_engine.py, csrc/ends3d.hip) timed at the reference's --crop_size, 64^3
 (DESIGN.md section 4.5d): forward + backward with dx of NLayerDiscriminator(2, 64, 3) and PixelDiscriminator(2, 64) on volumes, batch 1
 and 4, under BatchNorm3d and InstanceNorm3d, the two norms interleaved in one process; then every launch of each plan on its own
 (event pairs around each call, in the plan's order): time, algorithmic TFLOP/s for the convs, GB/s for the passes.  The algorithmic
