@@ -540,6 +540,35 @@ int gs_pack_weight_segs(int n, const GsSegPackDesc* descs, int dtype, void* stre
 int gs_conv3x3_precise(const void* x, const void* w, void* y_hi, void* y_lo, const float* bias, float* bn_partials, int N,
                        int H, int W, int K, int in_pix_stride, int in_coff, int in_wrap, int Cout, int out_pix_stride,
                        int out_coff, const int32_t* tap_dy, const int32_t* tap_dx, int act, int dtype, void* stream);
+/* ---- layout of a conv-output lo plane: 0 dense NHWC / 1 FRAGMENT ORDER --------------------------------------
+ * The lo plane of a conv output has one reader (the BatchNorm apply pass, or the head for the last stage).  Where the 8-wave LDS-DMA
+ * form runs a pair-forward launch whose items are all full 16 x 32 pixel x 64 cout tiles, it writes lo straight from its accumulator
+ * registers: the same number of elements, the tile of item = ((n * H/16 + ty) * W/32 + tx) * Cout/64 + cout tile stored as the lanes
+ * hold it -- wave w, pixel row i, cout half j, register group g, lane l = 32 h + l31 write 16 bytes at
+ *     (((((item * 8 + w) * 2 + i) * 2 + j) * 2 + g) * 64 + l) * 16,
+ * dword q of them = the 16-bit pair (pixel x, pixel x + 1) of cout 64 * tile + 32 j + l31 at y = 16 ty + 2 w + i,
+ * x = 32 tx + 16 g + 8 (q >> 1) + 4 h + 2 (q & 1).  The reader transposes; every stored result is what the dense layout gives.
+ * gs_conv3x3_pair_lo_layout: the layout a gs_conv3x3_precise_lo launch of these dimensions may use (1 only with H % 16 == 0,
+ *   W % 32 == 0, Cout % 64 == 0 on the 8-wave form); ask it once per stage and hand the answer to producer and reader.
+ * gs_pair_lo_set_layout: process-wide override, -1 automatic / 0 dense everywhere (tests, A/B runs).
+ * gs_conv3x3_precise_lo: gs_conv3x3_precise with the layout stated.  lo_layout 1 additionally needs BatchNorm partials, no bias, no
+ *   activation, forward taps and a dense output (out_pix_stride == Cout, out_coff == 0): GS_EINVAL before any launch otherwise.
+ * gs_bn_act_apply_split_lo / gs_head1x1_bn_fwd_split_lo / gs_head1x1_labels_lo: the readers with the layout of y_lo / x_lo stated
+ *   (lo_layout 1: H % 16 == 0, W % 32 == 0, C % 64 == 0; the heads 1..4 classes; GS_EINVAL otherwise).  The apply pass honours bit 1
+ *   of gs_bn_set_traversal. */
+int gs_conv3x3_pair_lo_layout(int N, int H, int W, int K, int Cout);
+int gs_pair_lo_set_layout(int mode);
+int gs_conv3x3_precise_lo(const void* x, const void* w, void* y_hi, void* y_lo, const float* bias, float* bn_partials, int N,
+                          int H, int W, int K, int in_pix_stride, int in_coff, int in_wrap, int Cout, int out_pix_stride,
+                          int out_coff, const int32_t* tap_dy, const int32_t* tap_dx, int act, int dtype, int lo_layout, void* stream);
+int gs_bn_act_apply_split_lo(const void* y_hi, const void* y_lo, const float* scale, const float* shift, int act, void* z_hi,
+                             void* z_lo, int z_pix_stride, int z_coff, void* zp_hi, void* zp_lo, int zp_pix_stride, int N,
+                             int H, int W, int C, int dtype, int lo_layout, void* stream);
+int gs_head1x1_bn_fwd_split_lo(const void* y_hi, const void* y_lo, const float* scale, const float* shift, int act, const float* w,
+                               const float* bias, float* logits, int N, int H, int W, int Cin, int Cout, int dtype, int lo_layout,
+                               void* stream);
+int gs_head1x1_labels_lo(const void* x_hi, const void* x_lo, const float* scale, const float* shift, int act, const float* w,
+                         const float* bias, uint8_t* labels, int N, int H, int W, int ncls, int dtype, int lo_layout, void* stream);
 /* ---- "q" stages: the correction terms of a pair-forward conv as ONE FP8 block-scaled MFMA segment ----------
  * A conv on hi/lo pairs needs x_hi.w_hi + x_lo.w_hi + x_hi.w_lo to meet 1e-3 on the logits (unet_parts.py:16,19 are plain fp32); the
  * two correction terms are 2^-11 of the main product, so 4 significant bits suffice for them: they run as e4m3 operands on

@@ -177,6 +177,12 @@ PROTOTYPES = {
     "gs_maxpool3d_fwd_pair": (c_int, [_P, _P, c_int, _P, _P] + [c_int] * 7 + [c_void_p]),
     "gs_upsample2x_bilinear_fwd_pair": (c_int, [_P, _P, _P, _P] + [c_int] * 13 + [c_void_p]),
     "gs_conv3x3_precise": (c_int, [_P, _P, _P, _P, _F, _F] + [c_int] * 10 + [POINTER(c_int32), POINTER(c_int32), c_int, c_int, c_void_p]),
+    "gs_conv3x3_pair_lo_layout": (c_int, [c_int] * 5),
+    "gs_pair_lo_set_layout": (c_int, [c_int]),
+    "gs_conv3x3_precise_lo": (c_int, [_P, _P, _P, _P, _F, _F] + [c_int] * 10 + [POINTER(c_int32), POINTER(c_int32), c_int, c_int, c_int, c_void_p]),
+    "gs_bn_act_apply_split_lo": (c_int, [_P, _P, _F, _F, c_int, _P, _P, c_int, c_int, _P, _P] + [c_int] * 7 + [c_void_p]),
+    "gs_head1x1_bn_fwd_split_lo": (c_int, [_P, _P, _F, _F, c_int, _F, _F, _F] + [c_int] * 7 + [c_void_p]),
+    "gs_head1x1_labels_lo": (c_int, [_P, _P, _F, _F, c_int, _F, _F, _P] + [c_int] * 6 + [c_void_p]),
     "gs_upconv2x2_fwd_precise": (c_int, [_P, _P, _F, _P, _P] + [c_int] * 15 + [c_void_p]),
     "gs_conv_smallcin_fwd_split": (c_int, [_F, _F, _P, _P, _F] + [c_int] * 8 + [c_void_p]),
     "gs_bn_act_apply_split": (c_int, [_P, _P, _F, _F, c_int, _P, _P, c_int, c_int, _P, _P] + [c_int] * 6 + [c_void_p]),

@@ -690,6 +690,8 @@ int reduce_partials(const float* partials, int ntiles, int C, double** out, int*
 
 }  // namespace
 
+int bn_traversal_mask() { return bn_traversal(); }          // (precise.hip: the fragment-order apply passes honour bit 1 too)
+
 // Size (in floats) a partials buffer needs for `ntiles` tiles of C channels, including the stage-1 area.
 extern "C" int64_t gs_bn_partials_floats(int ntiles, int C) {
     return (int64_t)ntiles * 2 * C + 4 + (int64_t)RED_SLICES * 2 * C * 2;

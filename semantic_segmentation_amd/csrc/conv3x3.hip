@@ -1088,6 +1088,25 @@ static C3DmaPlan c3_dma_plan(int N, int H, int W, int Cout, bool per_block_rows,
     return p;
 }
 
+// ---- layout of the conv-output lo plane of the pair forward: 0 dense NHWC / 1 fragment order (conv3x3_args.hpp) ----
+// The shape part of the decision, shared by the producer (conv3x3_launch) and, through gs_conv3x3_pair_lo_layout(), by the callers
+// that hand the plane to its one reader: the 8-wave form of the LDS-DMA kernel with nothing but full 16 x 32 x 64 items.  The
+// launch adds its own conditions (statistics, no bias, no activation, forward taps, a dense output): c3_pair_lo_frag_launch_ok().
+static std::atomic<int> c3_pair_lo_mode{-1};               // -1 automatic / 0 dense everywhere (tests, A/B runs)
+extern "C" int gs_pair_lo_set_layout(int mode) {
+    GS_CHECK_ARG(mode == -1 || mode == 0, "gs_pair_lo_set_layout: mode must be -1 (automatic) or 0 (dense lo planes)");
+    c3_pair_lo_mode.store(mode, std::memory_order_relaxed);
+    return GS_OK;
+}
+static bool c3_pair_lo_frag_ok(int N, int H, int W, int K, int Cout) {
+    static const int prec_dma = getenv("GSSEG_C3_PREC_DMA") ? atoi(getenv("GSSEG_C3_PREC_DMA")) : 1;
+    if (c3_pair_lo_mode.load(std::memory_order_relaxed) == 0 || prec_dma == 0) return false;
+    if (N <= 0 || H <= 0 || W <= 0 || H % 16 != 0 || W % 32 != 0 || Cout % 64 != 0 || K % 64 != 0) return false;
+    if (!c3_dma_shape_ok(W, K, Cout)) return false;
+    return c3_dma_plan(N, H, W, Cout, true, 0, true).waves == 8;
+}
+extern "C" int gs_conv3x3_pair_lo_layout(int N, int H, int W, int K, int Cout) { return c3_pair_lo_frag_ok(N, H, W, K, Cout) ? 1 : 0; }
+
 // Rows of BatchNorm partial sums ([rows][2][Cout] fp32) a gs_conv3x3 / gs_conv3d_3x3x3 / gs_conv3x3_precise launch with these
 // dimensions writes -- what gs_bn_finalize / gs_bn_partials_colsum must be told.  The LDS-DMA kernel keeps its sums in
 // registers across the items of a block and writes ONE row per block and cout-tile group (the pair forward too: `pair` tells
@@ -1106,8 +1125,10 @@ extern "C" int gs_conv3x3_stat_rows(int N, int H, int W, int Cin, int Cout, int 
 static int conv3x3_launch(const void* x, const void* w, void* y, const float* bias, float* bn_partials, int N, int H,
                           int W, int Cin, int in_pix_stride, int in_coff, int Cout, int out_pix_stride, int out_coff,
                           const int32_t* tap_dy, const int32_t* tap_dx, int act, int dtype, void* stream, int D, int ndz,
-                          const int32_t* tap_dz, void* y_lo = nullptr, int in_wrap = 0, const int* wexp = nullptr, int in_wrap_to = 0) {
+                          const int32_t* tap_dz, void* y_lo = nullptr, int in_wrap = 0, const int* wexp = nullptr, int in_wrap_to = 0,
+                          int lo_layout = 0) {
     GS_CHECK_ARG(x && w && y && tap_dy && tap_dx, "gs_conv3x3: null pointer");
+    GS_CHECK_ARG(lo_layout == 0 || lo_layout == 1, "gs_conv3x3_precise_lo: lo_layout must be 0 (dense) or 1 (fragment order)");
     GS_CHECK_ARG(N > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 8 == 0 && Cout > 0, "gs_conv3x3: bad dims");
     const bool prec = y_lo != nullptr;
     // precise mode: Cin is the K extent (segments x channels); the input holds in_wrap channels
@@ -1174,8 +1195,15 @@ static int conv3x3_launch(const void* x, const void* w, void* y, const float* bi
         const bool dma = c3_dma_shape_ok(W, Cin, Cout) && (prec ? (std_taps && prec_dma_env != 0) : (std_taps || flip_taps));
         GS_CHECK_ARG(wexp == nullptr || (dma && dtype == GS_F16 && Cin % 128 == 0),
                      "gs_conv3x3_q8: needs the LDS-DMA kernel (W >= 24, channels %% 64 == 0, Cout %% 8 == 0, forward taps) and fp16");
+        // a fragment-order lo plane: only where gs_conv3x3_pair_lo_layout() says so AND the launch is the plain training form -- a
+        // mismatch between what the caller asked for and what the kernel would write is an error, never a silent dense plane
+        GS_CHECK_ARG(lo_layout == 0 || (dma && prec && wexp == nullptr && ndz == 1 && bn_partials != nullptr && bias == nullptr &&
+                                        (act & 0xff) == GS_ACT_NONE && out_pix_stride == Cout && out_coff == 0 &&
+                                        c3_pair_lo_frag_ok(N, H, W, Cin, Cout)),
+                     "gs_conv3x3_precise_lo: fragment order needs gs_conv3x3_pair_lo_layout() == 1, statistics, no bias, no activation and a dense output");
         if (dma) {
             const C3DmaPlan dp = c3_dma_plan(N, H, W, Cout, true, wexp ? Cin / 2 : 0, prec);
+            a.lo_frag = lo_layout;
             a.tiles_x = dp.tiles_x; a.tiles_y = dp.tiles_y; a.ntn = dp.ntn; a.nblocks = dp.nitems;
             a.xcd_order = (xcd_env && (dp.grid % 8) == 0 && a.ntn > 1 && (int64_t)N * H * W > (int64_t)18 * Cout) ? 1 : 0;
             c3_dma_launch(a, dp.waves, prec, dtype, dp.grid, bs);
@@ -1216,6 +1244,7 @@ static int conv3x3_launch(const void* x, const void* w, void* y, const float* bi
         GS_CHECK_LAUNCH("gs_conv3x3");
         return GS_OK;
     }
+    GS_CHECK_ARG(lo_layout == 0, "gs_conv3x3_precise_lo: fragment order outside the LDS-DMA kernel");
     GS_CHECK_ARG(bn_partials == nullptr || !c3_dma_shape_ok(W, Cin, Cout),
                  "gs_conv3x3: BatchNorm partials with channel strides / offsets that are not multiples of 8 (gs_conv3x3_stat_rows would be wrong)");
     GS_CHECK_ARG(!prec, "gs_conv3x3_precise: needs the big-K-step kernel (GSSEG_C3=2, Cout %% 8 == 0, 16-byte aligned output channels)");
@@ -1279,6 +1308,18 @@ extern "C" int gs_conv3x3_precise(const void* x, const void* w, void* y_hi, void
     GS_CHECK_ARG(y_lo != nullptr, "gs_conv3x3_precise: y_lo is NULL");
     return conv3x3_launch(x, w, y_hi, bias, bn_partials, N, H, W, K, in_pix_stride, in_coff, Cout, out_pix_stride, out_coff,
                           tap_dy, tap_dx, act, dtype, stream, 1, 1, nullptr, y_lo, in_wrap);
+}
+
+// The same with the layout of the lo plane stated by the caller: 0 = dense NHWC (gs_conv3x3_precise), 1 = fragment order
+// (conv3x3_args.hpp; y_lo is then a plain N*H*W*Cout element buffer that only gs_bn_act_apply_split_lo / gs_head1x1_*_lo with the
+// same layout can read).  GS_EINVAL -- and no launch -- when fragment order is asked for on a launch that is not eligible.
+extern "C" int gs_conv3x3_precise_lo(const void* x, const void* w, void* y_hi, void* y_lo, const float* bias, float* bn_partials,
+                                     int N, int H, int W, int K, int in_pix_stride, int in_coff, int in_wrap, int Cout,
+                                     int out_pix_stride, int out_coff, const int32_t* tap_dy, const int32_t* tap_dx, int act,
+                                     int dtype, int lo_layout, void* stream) {
+    GS_CHECK_ARG(y_lo != nullptr, "gs_conv3x3_precise_lo: y_lo is NULL");
+    return conv3x3_launch(x, w, y_hi, bias, bn_partials, N, H, W, K, in_pix_stride, in_coff, Cout, out_pix_stride, out_coff,
+                          tap_dy, tap_dx, act, dtype, stream, 1, 1, nullptr, y_lo, in_wrap, nullptr, 0, lo_layout);
 }
 
 // 3x3x3 / stride 1 / pad 1 Conv3d (GenSeg-3D/UNet3D/unet3d.py:28-31,69-71) and its data gradient on the same halo-reuse

@@ -27,7 +27,20 @@ struct C3Args {
     // = the power-of-two exponent of cout row co's e4m3 weight planes (gs_pack_weight_q8).  q8_c0 = 0: none.
     int q8_c0 = 0;
     const int* wexp = nullptr;
+    // pair forward on the LDS-DMA kernel, 8-wave form: the lo plane leaves in FRAGMENT ORDER (conv3x3_dma.hip)
+    // instead of dense NHWC.  Set only for launches c3_pair_lo_frag_ok() admits: every item a full 16x32x64 tile.
+    int lo_frag = 0;
 };
+
+// Fragment order of a conv-output lo plane (the same number of elements as the dense plane).  The 16 x 32 pixel x 64 cout tile of
+// item = ((n * tiles_y + ty) * tiles_x + tx) * ntn + cout tile (tiles_y = H / 16, tiles_x = W / 32, ntn = Cout / 64) is stored as the
+// lanes of the conv hold it: wave w (patch rows 2w, 2w + 1), pixel row i, cout half j, register group g, lane l = 32 h + l31 writes
+// the 16 bytes at
+//     (((((item * 8 + w) * 2 + i) * 2 + j) * 2 + g) * 64 + l) * 16,
+// dword q = 0..3 of them = the pair (lo 16 bits: pixel x, hi 16 bits: pixel x + 1) of cout 64 * tile + 32 j + l31 at
+//     y = 16 ty + 2 w + i,  x = 32 tx + 16 g + 8 (q >> 1) + 4 h + 2 (q & 1).
+// One (item, w, i) -- a 32-pixel row x 64 couts -- is 4 KB contiguous: the unit of the readers (precise.hip).
+constexpr int C3_FRAG_TILE_B = 4096;
 
 constexpr int C3_LDR = 72;
 

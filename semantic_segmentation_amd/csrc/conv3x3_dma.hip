@@ -29,6 +29,13 @@
 //     running statistics); the transposition (8 passes of 8 pixel rows through a PRIVATE 1 KB LDS buffer per wave: 4
 //     ds_write_b32, one ds_read_b128, one 16-byte store each) is spread over the steps of the next item's first stage, two
 //     steps per pass.  Items with an activation (inference) or a partial patch take the immediate path.
+//   PREC with a FRAGMENT-ORDER lo plane (C3Args::lo_frag; the map is in conv3x3_args.hpp): the lo plane of a conv output has one
+//     reader, an HBM-bound pass that can transpose for nothing, so lo leaves straight from the accumulator registers -- lane l of
+//     wave w writes, per pixel row i, cout half j and register group g, the 16 bytes pack2(lo(r0), lo(r0 + 1)) of its four m values
+//     at (((((item * 8 + w) * 2 + i) * 2 + j) * 2 + g) * 64 + l) * 16.  That leaves 32 packed hi registers to defer, the 16-bit
+//     form's budget: the 8-wave DEFER + PREC instance (FRAGD) defers the hi transposition exactly as the 16-bit form does; with
+//     GSSEG_PAIR_LO_DEFER=0 the launch stays on the DEFER = false instance, whose immediate epilogue then skips lo's DPP / v_perm /
+//     staging work (FRAG).  Only launches whose items are all full, plain patches get here (conv3x3.hip: c3_pair_lo_frag_ok()).
 // Both forms keep the BatchNorm partial sums in registers across ALL items of the block (a block keeps its cout tile: the grid
 // is a multiple of the tile count) and write them once at the end: one row per block instead of one per half-item
 // (c3_dma_grid() rows; no LDS hand-over and barrier per item, no first-stage reduction launch afterwards).
@@ -58,7 +65,10 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
     typedef typename Elem<DT>::V8 V8;
     // the pair epilogue is deferred only in the 4-wave form: one wave per SIMD has the 512-register file to itself, so the 64
     // registers of packed hi + lo results can ride through the next item's first stage (the 8-wave form has 256 per wave)
-    static_assert(!(PREC && DEFER) || NWV == 4, "the deferred pair epilogue needs the 4-wave form's registers");
+    // ... or, in the 8-wave form, a lo plane in fragment order (FRAGD): lo leaves from the registers at the item boundary and only
+    // the 32 packed hi registers ride along -- the budget of the 16-bit deferred form
+    static_assert(!(PREC && DEFER) || NWV == 4 || (NWV == 8 && !Q8), "the deferred pair epilogue: 4 waves, or 8 waves with a fragment-order lo plane");
+    constexpr bool FRAGD = PREC && DEFER && NWV == 8;      // launched only with C3Args::lo_frag (every item full, no bias, no activation)
     static_assert(MI == 2 || (MI == 4 && NWV == 4 && DEFER), "the quad form: 4 waves, deferred epilogue");
     static_assert(!Q8 || PREC, "FP8 correction stages belong to the pair forward");
     constexpr int BN = 64, TW = 32, TH = MI * NWV, TWS = 5, KC = 32;
@@ -78,7 +88,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
     // staging overlays halo 1 + weights 1 (the last stage of an item always sits in buffer 1, the next item's first stage
     // is on its way into buffer 0)
     constexpr int H0_OFF = W_B, W1_OFF = W_B + 2 * HALO_B;
-    constexpr int PRIV_OFF = 2 * STAGE_B, PRIV_B = DEFER ? (PREC ? 2 : 1) * NWV * 1024 : 0;       // (PREC: a second buffer per wave for the lo halves)
+    constexpr int PRIV_OFF = 2 * STAGE_B, PRIV_B = DEFER ? ((PREC && !FRAGD) ? 2 : 1) * NWV * 1024 : 0;       // (PREC: a second buffer per wave for the lo halves)
     constexpr int LDS_B = 2 * STAGE_B + PRIV_B;
     static_assert(LDS_B <= 160 * 1024, "the stage buffers must fit in LDS");
     // PREC (precise mode): K is a concatenation of segments over the same input channels (stage c reads
@@ -226,7 +236,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
     // ---- deferred epilogue state (DEFER): the previous item's tile as packed 16-bit pairs, its store base, its image ----
     constexpr int NPK = DEFER ? 8 : 1;
     unsigned pk[MI][2][NPK];                                // [i][j][m]: rows 2m, 2m+1 of the lane's cout in tile (i, j)
-    constexpr int NPKL = (DEFER && PREC) ? 8 : 1;
+    constexpr int NPKL = (DEFER && PREC && !FRAGD) ? 8 : 1;
     unsigned pkl[MI][2][NPKL];                              // PREC: the lo halves of the same pairs
     unsigned pend_voff = MI == 4 ? 0x80000000u : 0u;       // lane part of the store offset of the pending tile (quad form: out of range = nothing pending)
     int pend_n = 0;                                        // its image
@@ -251,8 +261,8 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
                 const unsigned v = __builtin_amdgcn_perm(oth, own, psel);
                 const int slot = (j * 4 + (l31 >> 3)) ^ lr;                  // 16-byte slot (8 couts) of cout pair l31 & ~1
                 *reinterpret_cast<unsigned*>(priv + lr * 128 + slot * 16 + (l31 & 6) * 2) = v;
-                if (PREC) {
-                    const unsigned ownl = pkl[i][j][(DEFER && PREC) ? m : 0];
+                if (PREC && !FRAGD) {
+                    const unsigned ownl = pkl[i][j][NPKL == 8 ? m : 0];
                     const unsigned othl = (unsigned)__builtin_amdgcn_mov_dpp((int)ownl, 0xB1, 0xf, 0xf, true);
                     *reinterpret_cast<unsigned*>(priv + NWV * 1024 + lr * 128 + slot * 16 + (l31 & 6) * 2) = __builtin_amdgcn_perm(othl, ownl, psel);
                 }
@@ -265,7 +275,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
     const unsigned priv_rd = (unsigned)(PRIV_OFF + wave * 1024 + (lane >> 3) * 128 + (((lane & 7) ^ (lane >> 3)) << 4));
     auto defer_read = [&](int p) __attribute__((always_inline)) {
         asm volatile("ds_read_b128 %0, %1" : "=v"(dsv) : "v"(priv_rd) : "memory");
-        if (PREC) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dsvl) : "v"(priv_rd), "n"(NWV * 1024) : "memory");
+        if (PREC && !FRAGD) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dsvl) : "v"(priv_rd), "n"(NWV * 1024) : "memory");
     };
     auto defer_wait = [&]() __attribute__((always_inline)) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -276,8 +286,13 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
         const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
             (void*)(a.y + (int64_t)pend_n * a.H * a.W * a.out_stride), 0, (unsigned)a.H * a.W * a.out_stride * 2u, 0x00020000);
         const unsigned soff = (unsigned)i * row_stride_b + (unsigned)((p & 3) * 8) * (unsigned)a.out_stride * 2u;
-        __builtin_amdgcn_raw_buffer_store_b128(dsv, ry, pend_voff, soff, GS_OUT_AUX);
-        if (PREC) {
+        // (FRAGD: the scalar part rides in the vector offset -- one v_add -- and the scalar offset stays 0.  Behind a 16-byte store
+        // with an SGPR offset hipcc puts no wait states in front of a VALU write of the store's data registers, and the next pass's
+        // DPP / v_perm results may be given exactly those registers.  In the flush after a block's last item nothing stands between
+        // the passes: with one item per block -- every tile goes through the flush -- results then changed from run to run.)
+        if (FRAGD) __builtin_amdgcn_raw_buffer_store_b128(dsv, ry, pend_voff + soff, 0, GS_OUT_AUX);
+        else __builtin_amdgcn_raw_buffer_store_b128(dsv, ry, pend_voff, soff, GS_OUT_AUX);
+        if (PREC && !FRAGD) {
             const __amdgpu_buffer_rsrc_t ryl = __builtin_amdgcn_make_buffer_rsrc(
                 (void*)(a.y_lo + (int64_t)pend_n * a.H * a.W * a.out_stride), 0, (unsigned)a.H * a.W * a.out_stride * 2u, 0x00020000);
             __builtin_amdgcn_raw_buffer_store_b128(dsvl, ryl, pend_voff, soff, GS_OUT_AUX);
@@ -474,9 +489,13 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
     unsigned short* stg = reinterpret_cast<unsigned short*>(smem + H0_OFF + HALO_B) + wave * STG_EL;
     unsigned short* stg_lo = stg + NWV * STG_EL;                                        // PREC: the lo halves
     const float neg_slope = act == GS_ACT_RELU ? 0.f : (act == GS_ACT_LEAKY02 ? 0.2f : 1.f);
-    auto epilogue_t = [&](const Item& itc, auto plain_tag, auto full_tag) __attribute__((always_inline)) {
+    // FRAG (C3Args::lo_frag, a full patch of a plain pair launch in the 8-wave form): the lo half leaves STRAIGHT FROM THE
+    // REGISTERS in fragment order -- no DPP, no v_perm, no staging write or read-back for it; its one reader transposes it
+    auto epilogue_t = [&](const Item& itc, auto plain_tag, auto full_tag, auto frag_tag, int item_no = 0) __attribute__((always_inline)) {
         constexpr bool PLAIN = decltype(plain_tag)::value;
         constexpr bool FULL = decltype(full_tag)::value;
+        constexpr bool FRAG = decltype(frag_tag)::value;
+        static_assert(!FRAG || (PREC && PLAIN && FULL && NWV == 8 && MI == 2), "fragment-order lo: full plain items of the 8-wave pair form");
         int e_y0 = itc.y0, e_x0 = itc.x0, e_n = itc.n, e_n0 = itc.n0;
         asm volatile("" : "+s"(e_y0), "+s"(e_x0), "+s"(e_n), "+s"(e_n0));
         // (Q8: the staging addresses are re-formed per item from an opaque lane offset.  Left alone, hipcc hoists the ~40 per-lane
@@ -489,6 +508,9 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
             (void*)(a.y + (int64_t)e_n * a.H * a.W * a.out_stride), 0, (unsigned)a.H * a.W * a.out_stride * 2u, 0x00020000);
         const __amdgpu_buffer_rsrc_t ry_lo = __builtin_amdgcn_make_buffer_rsrc(
             (void*)((PREC ? a.y_lo : a.y) + (int64_t)e_n * a.H * a.W * a.out_stride), 0, (unsigned)a.H * a.W * a.out_stride * 2u, 0x00020000);
+        // fragment order: the item's 64 KB start at item * 64 KB of the lo plane (a 64-bit base: the lane offsets stay small)
+        const __amdgpu_buffer_rsrc_t ry_frag = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)((PREC ? a.y_lo : a.y) + (FRAG ? (int64_t)item_no * (TH * TW * BN) : 0)), 0, (unsigned)(TH * TW * BN * 2), 0x00020000);
         constexpr bool want_stats = STATS;              // BatchNorm partial sums: a template flag (no per-element selects)
         float bv[2] = {0.f, 0.f};
         if (!PLAIN) {
@@ -501,6 +523,9 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             const int prow0 = (wave * MI + i) * 32;
+            u32x4 lov[2];                                  // FRAG: the lane's lo pairs of register group g = m / 4, per cout half
+            unsigned frag_voff = (unsigned)(wave * 8192 + i * 4096 + lane * 16);      // (opaque: one register, not one per store)
+            if (FRAG) opaque_vgpr(frag_voff);
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 const int r0 = 2 * m;
@@ -538,10 +563,21 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
                         const float l0 = v0 - Elem<DT>::to_f((unsigned short)(own & 0xffffu));
                         const float l1 = v1 - Elem<DT>::to_f((unsigned short)(own >> 16));
                         const unsigned int own_l = Elem<DT>::pack2(l0, l1);
-                        const unsigned int oth_l = dpp_xor1(own_l);
-                        const unsigned int pk_l = __builtin_amdgcn_perm(oth_l, own_l, psel);
-                        if (Q8) *reinterpret_cast<unsigned int*>(stg_base + stg_b + (unsigned)((NWV * STG_EL + row * C3_LDR + j * 32) * 2)) = pk_l;
-                        else *reinterpret_cast<unsigned int*>(stg_lo + row * C3_LDR + j * 32 + (l31 & ~1)) = pk_l;
+                        if (FRAG) {
+                            lov[j][m & 3] = own_l;
+                            // offset ((((item * 8 + w) * 2 + i) * 2 + j) * 2 + g) * 64 + l) * 16.  The wave part rides in the VECTOR
+                            // offset and (j, g) in the instruction's immediate, the scalar offset stays 0: behind a 16-byte store
+                            // with an SGPR offset hipcc leaves out the wait states that keep the next VALU write off the store's data
+                            // registers, and here they are rewritten at once (measured: dword 3 of lanes 12..15 of a row lost)
+                            if ((m & 3) == 3)
+                                __builtin_amdgcn_raw_buffer_store_b128(lov[j], ry_frag,
+                                                                       frag_voff + (unsigned)((j * 2 + (m >> 2)) * 1024), 0, GS_OUT_AUX);
+                        } else {
+                            const unsigned int oth_l = dpp_xor1(own_l);
+                            const unsigned int pk_l = __builtin_amdgcn_perm(oth_l, own_l, psel);
+                            if (Q8) *reinterpret_cast<unsigned int*>(stg_base + stg_b + (unsigned)((NWV * STG_EL + row * C3_LDR + j * 32) * 2)) = pk_l;
+                            else *reinterpret_cast<unsigned int*>(stg_lo + row * C3_LDR + j * 32 + (l31 & ~1)) = pk_l;
+                        }
                     }
                 }
             }
@@ -562,7 +598,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
                 d[0] = sv[q].x; d[1] = sv[q].y; d[2] = sv[q].z; d[3] = sv[q].w;
                 if (dbg & 64) asm volatile("" :: "v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]), "v"(off));      // ablation: no global stores
                 else __builtin_amdgcn_raw_buffer_store_b128(d, ry, off, 0, GS_OUT_AUX);
-                if (PREC) {
+                if (PREC && !FRAG) {
                     const uint4 lv = Q8 ? *reinterpret_cast<const uint4*>(stg_base + stg_rb + (unsigned)((NWV * STG_EL + q * 8 * C3_LDR) * 2))
                                         : *reinterpret_cast<const uint4*>(stg_lo + (q * 8 + (lane >> 3)) * C3_LDR + (lane & 7) * 8);
                     u32x4 dl;
@@ -574,14 +610,22 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
         }
     };
     const bool plain = (a.bias == nullptr && act == GS_ACT_NONE);
+    constexpr bool FRAG_OK = PREC && STATS && !DEFER && !Q8 && NWV == 8;     // the instances a fragment-order launch can reach (the host decides)
     const bool deferable = DEFER && act == GS_ACT_NONE;    // a bias rides along (bvb), an activation takes the immediate path
     // deferred form, item boundary: accumulators -> packed pairs + running statistics (nothing leaves the registers).  A bias
     // (Conv3d of the 3-D U-Net, unet3d.py:28-31) is added after the statistics, as on the immediate path; the block keeps its
     // cout tile, so the lane's two bias values are loaded once.
     float bvb[2] = {0.f, 0.f};
-    auto convert_item = [&](const Item& itc) __attribute__((always_inline)) {
+    auto convert_item = [&](const Item& itc, int item_no) __attribute__((always_inline)) {
+        // FRAGD: the lo half leaves here, in fragment order, as in the immediate epilogue's FRAG form (same offsets, same reason
+        // for the zero scalar offset)
+        const __amdgpu_buffer_rsrc_t ry_frag = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)((PREC ? a.y_lo : a.y) + (FRAGD ? (int64_t)item_no * (TH * TW * BN) : 0)), 0, (unsigned)(TH * TW * BN * 2), 0x00020000);
+        u32x4 lov[2];
 #pragma unroll
-        for (int i = 0; i < MI; ++i)
+        for (int i = 0; i < MI; ++i) {
+            unsigned frag_voff = (unsigned)(wave * 8192 + i * 4096 + lane * 16);      // (opaque: one register, not one per store)
+            if (FRAGD) opaque_vgpr(frag_voff);
 #pragma unroll
             for (int m = 0; m < 8; ++m)
 #pragma unroll
@@ -592,17 +636,29 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
                         s1v[j] += vv;
                         s2v[j] += vv * vv;
                     }
-                    v0 += bvb[j];
-                    v1 += bvb[j];
+                    if (!FRAGD) {
+                        v0 += bvb[j];
+                        v1 += bvb[j];
+                    }
                     unsigned own = Elem<DT>::pack2(v0, v1);
                     // (quad form: pinned here -- hipcc otherwise sinks the conversions to their uses in the next item's stages and
                     // carries the 128 fp32 values there in a second accumulator set: 560 registers)
                     if (MI == 4) opaque_vgpr(own);
                     pk[i][j][DEFER ? m : 0] = own;
-                    if (PREC)                                 // lo = 16-bit(value - hi): the pair carries ~22 bits
-                        pkl[i][j][(DEFER && PREC) ? m : 0] = Elem<DT>::pack2(v0 - Elem<DT>::to_f((unsigned short)(own & 0xffffu)),
-                                                                             v1 - Elem<DT>::to_f((unsigned short)(own >> 16)));
+                    if (PREC) {                               // lo = 16-bit(value - hi): the pair carries ~22 bits
+                        const unsigned own_l = Elem<DT>::pack2(v0 - Elem<DT>::to_f((unsigned short)(own & 0xffffu)),
+                                                               v1 - Elem<DT>::to_f((unsigned short)(own >> 16)));
+                        if (FRAGD) {
+                            lov[j][m & 3] = own_l;
+                            if ((m & 3) == 3)
+                                __builtin_amdgcn_raw_buffer_store_b128(lov[j], ry_frag,
+                                                                       frag_voff + (unsigned)((j * 2 + (m >> 2)) * 1024), 0, GS_OUT_AUX);
+                        } else {
+                            pkl[i][j][NPKL == 8 ? m : 0] = own_l;
+                        }
+                    }
                 }
+        }
         int e_y0 = itc.y0, e_x0 = itc.x0;
         asm volatile("" : "+s"(e_y0), "+s"(e_x0));
         // pixel (patch row 2*wave + i, column 8*(p & 3) + lane / 8), couts n0 + 8*(lane & 7): i and p ride in the scalar offset
@@ -773,8 +829,10 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
             PH(3);
         }
         const bool full = (cur.y0 + TH <= a.H) && (cur.x0 + TW <= a.W);
-        if (deferable && full && !(dbg & 4)) {
-            convert_item(cur);                             // registers only: no barrier, no LDS
+        if constexpr (FRAGD) {                             // every item is full and plain (the host's eligibility rule): no immediate path
+            if (!(dbg & 4)) convert_item(cur, it);         //   in this instance, and none of its staging addresses in registers
+        } else if (deferable && full && !(dbg & 4)) {
+            convert_item(cur, it);                         // registers only: no barrier, no LDS
         } else {
             if (DEFER) {                                   // (nothing is pending here; tells the register allocator so)
 #pragma unroll
@@ -788,10 +846,16 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv3x3_dma_kernel(const C3Args a
             asm volatile("" ::: "memory");
             if (!(dbg & 4)) {
                 if (Q8) {                                  // (a "q" stage has neither bias nor activation: no code for them in this kernel)
-                    if (full) epilogue_t(cur, std::true_type{}, std::true_type{});
-                    else epilogue_t(cur, std::true_type{}, std::false_type{});
-                } else if (plain && full) epilogue_t(cur, std::true_type{}, std::true_type{});
-                else epilogue_t(cur, std::false_type{}, std::false_type{});
+                    if (full) epilogue_t(cur, std::true_type{}, std::true_type{}, std::false_type{});
+                    else epilogue_t(cur, std::true_type{}, std::false_type{}, std::false_type{});
+                } else if (plain && full) {
+                    if constexpr (FRAG_OK) {
+                        if (a.lo_frag) epilogue_t(cur, std::true_type{}, std::true_type{}, std::true_type{}, it);
+                        else epilogue_t(cur, std::true_type{}, std::true_type{}, std::false_type{});
+                    } else {
+                        epilogue_t(cur, std::true_type{}, std::true_type{}, std::false_type{});
+                    }
+                } else epilogue_t(cur, std::false_type{}, std::false_type{}, std::false_type{});
             }
             // (no barrier behind it: the staging area is overwritten by DMA pieces only after the next stage hand-over)
         }
@@ -873,9 +937,15 @@ int c3_dma_launch(C3Args& a, int waves, bool prec, int dtype, int grid_blocks, h
         }
         return 0;
     }
+    // a fragment-order lo plane (8 waves, statistics: the host has checked the launch): the deferred hi epilogue, unless
+    // GSSEG_PAIR_LO_DEFER=0 asks for the immediate one (the A/B switch of tools/bench_pair_epilogue.py)
+    static const bool frag_defer = !(getenv("GSSEG_PAIR_LO_DEFER") && atoi(getenv("GSSEG_PAIR_LO_DEFER")) == 0);
 #define C3_DMA_GO(DT, NWV)                                                                                    \
     do {                                                                                                      \
-        if (prec) {                                            /* 4 waves: the deferred pair epilogue */      \
+        if (prec && NWV == 8 && a.lo_frag && frag_defer) {                                                    \
+            if (!stats) return -1;                                                                            \
+            conv3x3_dma_kernel<DT, 8, true, true, true><<<grid, 512, 0, s>>>(a);                              \
+        } else if (prec) {                                     /* 4 waves: the deferred pair epilogue */      \
             if (stats) conv3x3_dma_kernel<DT, NWV, true, true, NWV == 4><<<grid, 64 * NWV, 0, s>>>(a);        \
             else conv3x3_dma_kernel<DT, NWV, false, true, NWV == 4><<<grid, 64 * NWV, 0, s>>>(a);             \
         } else {                                                                                              \

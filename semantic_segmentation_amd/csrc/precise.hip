@@ -8,6 +8,7 @@
 //   gs_head1x1_fwd_split      OutConv (unet_parts.py:74) reading the z pair
 // Opt-in (UNet(..., precise=True)); the default engine stores single 16-bit values.
 #include "common.hpp"
+#include "conv3x3_args.hpp"      // the fragment order of a conv-output lo plane
 
 namespace {
 
@@ -496,6 +497,175 @@ __global__ __launch_bounds__(256) void bn_act_apply_split_pool_kernel(const Appl
     }
 }
 
+// ---- readers of a FRAGMENT-ORDER lo plane (conv3x3_args.hpp: what the 8-wave pair-forward conv writes straight from its
+// accumulator registers).  The unit of work is one wave and one 32-pixel row x 64 channels: 4 KB of lo, contiguous, read with
+// coalesced 16-byte loads exactly as the conv's lanes wrote them, and 32 runs of 128 B in y_hi.  The wave brings lo into pixel
+// order through a private 4 KB LDS tile (the conv's own DPP / v_perm / ds_write_b32 transposition, moved out of the MFMA-bound
+// kernel into these HBM-bound passes, whose VALU and LDS idle); wave barriers only.  Afterwards lane l holds, for pass q, the
+// 8-channel chunk l & 7 of pixel 8 q + l / 8 -- hi and lo -- and the arithmetic is that of the dense kernels, value for value.
+__device__ __forceinline__ void frag_lo_load(const unsigned char* lo_tile, int lane, uint4 (&v)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const uint4*>(lo_tile + k * 1024 + lane * 16);      // k = 2 j + g
+}
+// the lane's 16 dwords -> the tile [32 pixels][128 B]; the 16-byte slot s of pixel row r lives at s ^ (r & 7): the 64 lanes of
+// one write (rows r, r + 1, r + 4, r + 5; 16 dwords each) hit 64 distinct banks
+__device__ __forceinline__ void frag_lo_to_lds(unsigned char* tile, int lane, const uint4 (&v)[4]) {
+    const int l31 = lane & 31, h = lane >> 5, odd = lane & 1;
+    const unsigned psel = odd ? 0x03020706u : 0x05040100u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = k >> 1, g = k & 1;
+        const unsigned w[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            // own = (pixel x, pixel x + 1) of cout l31; with the neighbour lane's: (cout l31 & ~1, + 1) of pixel x + odd
+            const unsigned oth = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w[q], 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, false);
+            const unsigned pv = __builtin_amdgcn_perm(oth, w[q], psel);
+            const int row = 16 * g + 8 * (q >> 1) + 4 * h + 2 * (q & 1) + odd;
+            const int slot = (j * 4 + (l31 >> 3)) ^ (row & 7);
+            *reinterpret_cast<unsigned*>(tile + row * 128 + slot * 16 + (l31 & 6) * 2) = pv;
+        }
+    }
+}
+__device__ __forceinline__ uint4 frag_lo_read(const unsigned char* tile, int px, int chunk) {
+    return *reinterpret_cast<const uint4*>(tile + px * 128 + ((chunk ^ (px & 7)) << 4));
+}
+__device__ __forceinline__ void frag_wave_sync() {          // the wave's LDS writes are visible to its own lanes' reads (and vice versa)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// byte offset of the 4 KB of (image n, row y, patch column tx, cout tile ct) in a fragment-order plane
+__device__ __forceinline__ int64_t frag_tile_off(int n, int y, int tx, int ct, int H, int tiles_x, int ntn) {
+    const int64_t item = ((int64_t)(n * (H >> 4) + (y >> 4)) * tiles_x + tx) * ntn + ct;
+    return (item * 16 + (y & 15)) * C3_FRAG_TILE_B;
+}
+
+// Plain form.  A wave keeps its cout tile (host: ntn | waves of the grid), so scale / shift live in registers; the tiles of that
+// cout tile are taken in order, or tail first (rev: bit 1 of gs_bn_set_traversal -- the conv has just written the tail).  Four
+// pixels in flight per lane, hi and lo: eight 16-byte loads before the first use, as the dense kernel.
+template <int DT, bool LO>
+__global__ __launch_bounds__(256) void bn_act_apply_split_frag_kernel(const ApplySArgs a, int rev) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[4][C3_FRAG_TILE_B];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned char* const tile = lds[wv];
+    const float slope = a.act == GS_ACT_RELU ? 0.f : (a.act == GS_ACT_LEAKY02 ? 0.2f : 1.f);
+    const int ntn = a.C >> 6, tiles_x = a.W >> 5;
+    const int gw = blockIdx.x * 4 + wv, nw = gridDim.x * 4;
+    const int ct = gw % ntn;
+    const int chunk = lane & 7, pl = lane >> 3;
+    const int c0 = ct * 64 + chunk * 8;
+    float sc[8], sh[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { sc[i] = a.scale ? a.scale[c0 + i] : 1.f; sh[i] = a.shift ? a.shift[c0 + i] : 0.f; }
+    const int NT = a.N * a.H * tiles_x;                    // 32-pixel rows per cout tile (host: < 2^31)
+    for (int u = gw / ntn; u < NT; u += nw / ntn) {
+        const int uu = rev ? NT - 1 - u : u;
+        const int tx = uu % tiles_x, r = uu / tiles_x;
+        const int y = r % a.H, n = r / a.H;
+        const int64_t pix0 = ((int64_t)n * a.H + y) * a.W + tx * 32 + pl;
+        uint4 vl[4], vh[4];
+        frag_lo_load(reinterpret_cast<const unsigned char*>(a.y_lo) + frag_tile_off(n, y, tx, ct, a.H, tiles_x, ntn), lane, vl);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) vh[q] = *reinterpret_cast<const uint4*>(a.y_hi + (pix0 + q * 8) * a.C + c0);
+        frag_lo_to_lds(tile, lane, vl);
+        frag_wave_sync();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t p = pix0 + q * 8;
+            float v[8];
+            join8<DT>(vh[q], frag_lo_read(tile, q * 8 + pl, chunk), v);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float t = v[i] * sc[i] + sh[i];
+                v[i] = t > 0.f ? t : t * slope;
+            }
+            if (LO) {
+                uint4 hi, lo;
+                split8<DT>(v, hi, lo);
+                st16(a.z_hi + p * a.zs + a.zc + c0, hi);
+                st16(a.z_lo + p * a.zs + a.zc + c0, lo);
+            } else {
+                st16(a.z_hi + p * a.zs + a.zc + c0, pack8<DT>(v));
+            }
+        }
+        frag_wave_sync();
+    }
+}
+
+// Pooled form: a wave's two pixel rows i = 0, 1 of a patch are the two rows of the 2x2 windows, so it takes the strip of both (8 KB
+// of lo, 16 windows x 64 channels): lane l owns chunk l & 7 of the windows l / 8 and 8 + l / 8.  The pooled pair is the maximum
+// of the STORED pair values, in the window order of bn_act_apply_split_pool_kernel.
+template <int DT, bool LO>
+__global__ __launch_bounds__(256) void bn_act_apply_split_pool_frag_kernel(const ApplySArgs a, int rev) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[4][2 * C3_FRAG_TILE_B];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned char* const tile = lds[wv];
+    const float slope = a.act == GS_ACT_RELU ? 0.f : (a.act == GS_ACT_LEAKY02 ? 0.2f : 1.f);
+    const int ntn = a.C >> 6, tiles_x = a.W >> 5;
+    const int gw = blockIdx.x * 4 + wv, nw = gridDim.x * 4;
+    const int ct = gw % ntn;
+    const int chunk = lane & 7, pl = lane >> 3;
+    const int c0 = ct * 64 + chunk * 8;
+    float sc[8], sh[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { sc[i] = a.scale ? a.scale[c0 + i] : 1.f; sh[i] = a.shift ? a.shift[c0 + i] : 0.f; }
+    const int PH = a.H >> 1, PW = a.W >> 1;
+    const int NT = a.N * PH * tiles_x;                     // strips of 2 x 32 pixels per cout tile
+    for (int u = gw / ntn; u < NT; u += nw / ntn) {
+        const int uu = rev ? NT - 1 - u : u;
+        const int tx = uu % tiles_x, r = uu / tiles_x;
+        const int py = r % PH, n = r / PH;
+        const unsigned char* lo_strip = reinterpret_cast<const unsigned char*>(a.y_lo) + frag_tile_off(n, 2 * py, tx, ct, a.H, tiles_x, ntn);
+        uint4 vl[2][4], vh[2][4];                          // vh[s][q]: window 8 s + pl, pixel (row q / 2, column q & 1) of it
+        frag_lo_load(lo_strip, lane, vl[0]);
+        frag_lo_load(lo_strip + C3_FRAG_TILE_B, lane, vl[1]);
+        const int64_t pix00 = ((int64_t)n * a.H + 2 * py) * a.W + tx * 32;
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                vh[s][q] = *reinterpret_cast<const uint4*>(a.y_hi + (pix00 + (q >> 1) * a.W + 2 * (8 * s + pl) + (q & 1)) * a.C + c0);
+        frag_lo_to_lds(tile, lane, vl[0]);
+        frag_lo_to_lds(tile + C3_FRAG_TILE_B, lane, vl[1]);
+        frag_wave_sync();
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int wx = 8 * s + pl;
+            float mx[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) mx[i] = -INFINITY;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int xx = 2 * wx + (q & 1);
+                const int64_t pix = pix00 + (q >> 1) * a.W + xx;
+                float v[8];
+                join8<DT>(vh[s][q], frag_lo_read(tile + (q >> 1) * C3_FRAG_TILE_B, xx, chunk), v);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const float t = v[i] * sc[i] + sh[i];
+                    v[i] = t > 0.f ? t : t * slope;
+                }
+                uint4 hi, lo;
+                split8<DT>(v, hi, lo);
+                st16(a.z_hi + pix * a.zs + a.zc + c0, hi);
+                if (LO) st16(a.z_lo + pix * a.zs + a.zc + c0, lo);
+                float rr[8];
+                if (LO) join8<DT>(hi, lo, rr);
+                else unpack8<DT>(hi, rr);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) mx[i] = fmaxf(mx[i], rr[i]);
+            }
+            const int64_t pp = ((int64_t)n * PH + py) * PW + tx * 16 + wx;
+            uint4 hi, lo;
+            split8<DT>(mx, hi, lo);
+            st16(a.zp_hi + pp * a.zps + c0, hi);
+            if (a.zp_lo) st16(a.zp_lo + pp * a.zps + c0, lo);
+        }
+        frag_wave_sync();
+    }
+}
+
 // 3-D form (UNet3D's analysis blocks, GenSeg-3D/UNet3D/unet3d.py:29-36: BatchNorm3d + ReLU + MaxPool3d(2)): units are 2x2x2 windows of
 // the [NB*D, H, W] voxel grid (even D, H, W: host-checked), the eight voxels of a window are loaded before the first use; the z pair is
 // stored as bn_act_apply_split_kernel stores it and the pooled pair is the maximum of the STORED pair values -- bit-identical to
@@ -576,60 +746,98 @@ __device__ __forceinline__ float sum8_dpp_p(float v) {
 // LAB = true (gs_head1x1_labels): the label of the pixel leaves instead of its logits -- sigmoid(logit) > 0.5 for one class, else the
 // first maximum over the classes (the predicate of eval_dice_kernel, loss.hip) on exactly the values s[c] + bv[c] that the
 // logit flavour stores; lane 0 of the pixel writes the byte.
+// (FRAG: x_lo is a fragment-order plane, see the readers above -- a wave takes one 32-pixel row, brings its lo tile into pixel
+// order through LDS and then runs the four passes of 8 pixels with the lane roles of the dense form: same sums, same order.)
+struct HeadCoef { float w[4][8], bv[4], sc[8], sh[8], slope; };
+template <int DT>
+__device__ __forceinline__ void head_coef_load(const HeadSArgs& a, int ch, HeadCoef& k) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        k.bv[c] = (c < a.Cout && a.bias) ? a.bias[c] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) k.w[c][i] = c < a.Cout ? a.w[c * 64 + ch * 8 + i] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { k.sc[i] = a.scale ? a.scale[ch * 8 + i] : 1.f; k.sh[i] = a.scale ? a.shift[ch * 8 + i] : 0.f; }
+    k.slope = a.act == GS_ACT_RELU ? 0.f : (a.act == GS_ACT_LEAKY02 ? 0.2f : 1.f);
+}
+// pixel m from its joined pair chunk: the eight lanes of the pixel hold chunks 0..7
+template <int DT, bool LAB>
+__device__ __forceinline__ void head_pixel(const HeadSArgs& a, const HeadCoef& k, const uint4& xh, const uint4& xl, int m, int ch) {
+    float v[8], s[4];
+    join8<DT>(xh, xl, v);
+    if (a.scale) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float t = v[i] * k.sc[i] + k.sh[i];
+            v[i] = t > 0.f ? t : t * k.slope;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        float t = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) t += v[i] * k.w[c][i];
+        s[c] = sum8_dpp_p(t);
+    }
+    if (ch == 0) {
+        if constexpr (LAB) {
+            float best = s[0] + k.bv[0];
+            int pred = 0;
+            if (a.Cout == 1) {
+                pred = 1.f / (1.f + expf(-best)) > 0.5f ? 1 : 0;
+            } else {
+#pragma unroll
+                for (int c = 1; c < 4; ++c) {
+                    const float lv = s[c] + k.bv[c];
+                    if (c < a.Cout && lv > best) { best = lv; pred = c; }
+                }
+            }
+            a.lab[m] = (uint8_t)pred;
+        } else {
+            const int n = m / a.HW, hw = m - n * a.HW;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c < a.Cout) a.y[((int64_t)n * a.Cout + c) * a.HW + hw] = s[c] + k.bv[c];
+        }
+    }
+}
+
 template <int DT, bool LAB = false>
 __global__ __launch_bounds__(256) void head1x1_split_kernel(const HeadSArgs a) {
     const int ch = threadIdx.x & 7, pl = threadIdx.x >> 3;
-    float w[4][8], bv[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        bv[c] = (c < a.Cout && a.bias) ? a.bias[c] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) w[c][i] = c < a.Cout ? a.w[c * 64 + ch * 8 + i] : 0.f;
-    }
+    HeadCoef k;
+    head_coef_load<DT>(a, ch, k);
     const int M = a.N * a.HW;
-    float sc[8], sh[8];
+    for (int m = blockIdx.x * 32 + pl; m < M; m += gridDim.x * 32)
+        head_pixel<DT, LAB>(a, k, *reinterpret_cast<const uint4*>(a.x_hi + (int64_t)m * 64 + ch * 8),
+                            *reinterpret_cast<const uint4*>(a.x_lo + (int64_t)m * 64 + ch * 8), m, ch);
+}
+
+// H, W: the image (HW = H * W, H % 16 == 0, W % 32 == 0); one wave per 32-pixel row
+template <int DT, bool LAB = false>
+__global__ __launch_bounds__(256) void head1x1_split_frag_kernel(const HeadSArgs a, int H, int W) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[4][C3_FRAG_TILE_B];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned char* const tile = lds[wv];
+    const int ch = lane & 7, pl = lane >> 3;
+    HeadCoef k;
+    head_coef_load<DT>(a, ch, k);
+    const int tiles_x = W >> 5;
+    const int NT = a.N * H * tiles_x;
+    for (int u = blockIdx.x * 4 + wv; u < NT; u += gridDim.x * 4) {
+        const int tx = u % tiles_x, r = u / tiles_x;
+        const int y = r % H, n = r / H;
+        const int m0 = (n * H + y) * W + tx * 32 + pl;
+        uint4 vl[4], vh[4];
+        frag_lo_load(reinterpret_cast<const unsigned char*>(a.x_lo) + frag_tile_off(n, y, tx, 0, H, tiles_x, 1), lane, vl);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { sc[i] = a.scale ? a.scale[ch * 8 + i] : 1.f; sh[i] = a.scale ? a.shift[ch * 8 + i] : 0.f; }
-    const float slope = a.act == GS_ACT_RELU ? 0.f : (a.act == GS_ACT_LEAKY02 ? 0.2f : 1.f);
-    for (int m = blockIdx.x * 32 + pl; m < M; m += gridDim.x * 32) {
-        float v[8], s[4];
-        join8<DT>(*reinterpret_cast<const uint4*>(a.x_hi + (int64_t)m * 64 + ch * 8),
-                  *reinterpret_cast<const uint4*>(a.x_lo + (int64_t)m * 64 + ch * 8), v);
-        if (a.scale) {
+        for (int q = 0; q < 4; ++q) vh[q] = *reinterpret_cast<const uint4*>(a.x_hi + (int64_t)(m0 + q * 8) * 64 + ch * 8);
+        frag_lo_to_lds(tile, lane, vl);
+        frag_wave_sync();
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float t = v[i] * sc[i] + sh[i];
-                v[i] = t > 0.f ? t : t * slope;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float t = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) t += v[i] * w[c][i];
-            s[c] = sum8_dpp_p(t);
-        }
-        if (ch == 0) {
-            if constexpr (LAB) {
-                float best = s[0] + bv[0];
-                int pred = 0;
-                if (a.Cout == 1) {
-                    pred = 1.f / (1.f + expf(-best)) > 0.5f ? 1 : 0;
-                } else {
-#pragma unroll
-                    for (int c = 1; c < 4; ++c) {
-                        const float v = s[c] + bv[c];
-                        if (c < a.Cout && v > best) { best = v; pred = c; }
-                    }
-                }
-                a.lab[m] = (uint8_t)pred;
-            } else {
-                const int n = m / a.HW, hw = m - n * a.HW;
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    if (c < a.Cout) a.y[((int64_t)n * a.Cout + c) * a.HW + hw] = s[c] + bv[c];
-            }
-        }
+        for (int q = 0; q < 4; ++q) head_pixel<DT, LAB>(a, k, vh[q], frag_lo_read(tile, q * 8 + pl, ch), m0 + q * 8, ch);
+        frag_wave_sync();
     }
 }
 
@@ -852,7 +1060,18 @@ extern "C" int gs_conv_smallcin_fwd_split(const float* x, const float* w, void* 
 
 static int bn_act_apply_split_impl(const void* y_hi, const void* y_lo, const float* scale, const float* shift, int act,
                                    void* z_hi, void* z_lo, int z_pix_stride, int z_coff, void* zp_hi, void* zp_lo,
-                                   int zp_pix_stride, int N, int H, int W, int C, int dtype, void* stream, int z_q8, int zp_q8);
+                                   int zp_pix_stride, int N, int H, int W, int C, int dtype, void* stream, int z_q8, int zp_q8,
+                                   int lo_layout = 0);
+int bn_traversal_mask();                                   // bn.hip: the mask of gs_bn_set_traversal
+// the same with the layout of y_lo stated: 0 dense NHWC, 1 fragment order (what gs_conv3x3_precise_lo wrote with lo_layout 1;
+// needs H % 16 == 0, W % 32 == 0, C % 64 == 0).  Every output is what the dense form computes from the same values.
+extern "C" int gs_bn_act_apply_split_lo(const void* y_hi, const void* y_lo, const float* scale, const float* shift, int act,
+                                        void* z_hi, void* z_lo, int z_pix_stride, int z_coff, void* zp_hi, void* zp_lo,
+                                        int zp_pix_stride, int N, int H, int W, int C, int dtype, int lo_layout, void* stream) {
+    GS_CHECK_ARG(lo_layout == 0 || lo_layout == 1, "gs_bn_act_apply_split_lo: lo_layout must be 0 (dense) or 1 (fragment order)");
+    return bn_act_apply_split_impl(y_hi, y_lo, scale, shift, act, z_hi, z_lo, z_pix_stride, z_coff, zp_hi, zp_lo, zp_pix_stride, N, H, W,
+                                   C, dtype, stream, 0, 0, lo_layout);
+}
 extern "C" int gs_bn_act_apply_split(const void* y_hi, const void* y_lo, const float* scale, const float* shift, int act,
                                      void* z_hi, void* z_lo, int z_pix_stride, int z_coff, void* zp_hi, void* zp_lo,
                                      int zp_pix_stride, int N, int H, int W, int C, int dtype, void* stream) {
@@ -872,7 +1091,8 @@ extern "C" int gs_bn_act_apply_split_q8(const void* y_hi, const void* y_lo, cons
 }
 static int bn_act_apply_split_impl(const void* y_hi, const void* y_lo, const float* scale, const float* shift, int act,
                                    void* z_hi, void* z_lo, int z_pix_stride, int z_coff, void* zp_hi, void* zp_lo,
-                                   int zp_pix_stride, int N, int H, int W, int C, int dtype, void* stream, int z_q8, int zp_q8) {
+                                   int zp_pix_stride, int N, int H, int W, int C, int dtype, void* stream, int z_q8, int zp_q8,
+                                   int lo_layout) {
     GS_CHECK_ARG(y_hi && y_lo && z_hi && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "gs_bn_act_apply_split: bad arguments");
     GS_CHECK_ARG(z_pix_stride >= z_coff + C && z_pix_stride % 8 == 0 && z_coff % 8 == 0, "gs_bn_act_apply_split: bad z stride");
     GS_CHECK_ARG((scale == nullptr) == (shift == nullptr), "gs_bn_act_apply_split: scale/shift must both be given or NULL");
@@ -898,6 +1118,34 @@ static int bn_act_apply_split_impl(const void* y_hi, const void* y_lo, const flo
     while ((256 * bq) % nch != 0) ++bq;
     blocks = cdiv64(blocks, bq) * bq;
     hipStream_t s = (hipStream_t)stream;
+    if (lo_layout == 1) {
+        GS_CHECK_ARG(H % 16 == 0 && W % 32 == 0 && C % 64 == 0 && !z_q8 && !zp_q8,
+                     "gs_bn_act_apply_split_lo: a fragment-order lo plane needs H %% 16 == 0, W %% 32 == 0, C %% 64 == 0 and 16-bit lo planes");
+        GS_CHECK_ARG((int64_t)N * H * (W / 32) < 2147483000LL, "gs_bn_act_apply_split_lo: too many pixels");
+        GS_CHECK_ARG(((uintptr_t)y_hi | (uintptr_t)y_lo | (uintptr_t)z_hi | (uintptr_t)z_lo | (uintptr_t)zp_hi | (uintptr_t)zp_lo) % 16 == 0,
+                     "gs_bn_act_apply_split_lo: planes must be 16-byte aligned");
+        const int ntn = C / 64;
+        const int64_t tiles = (int64_t)N * (pool ? H / 2 : H) * (W / 32) * ntn;        // one wave each, four per block
+        int64_t fb = cdiv64(tiles, 4);
+        if (fb > 256 * 8) fb = 256 * 8;
+        fb = cdiv64(fb, ntn) * ntn;                        // a wave keeps its cout tile: ntn | waves of the grid
+        const int rev = bn_traversal_mask() & 1;
+#define GS_APPLY_FRAG(DT)                                                                                   \
+    do {                                                                                                    \
+        if (pool) {                                                                                         \
+            if (lof) bn_act_apply_split_pool_frag_kernel<DT, true><<<(int)fb, 256, 0, s>>>(a, rev);         \
+            else bn_act_apply_split_pool_frag_kernel<DT, false><<<(int)fb, 256, 0, s>>>(a, rev);            \
+        } else {                                                                                            \
+            if (lof) bn_act_apply_split_frag_kernel<DT, true><<<(int)fb, 256, 0, s>>>(a, rev);              \
+            else bn_act_apply_split_frag_kernel<DT, false><<<(int)fb, 256, 0, s>>>(a, rev);                 \
+        }                                                                                                   \
+    } while (0)
+        if (dtype == GS_F16) GS_APPLY_FRAG(GS_F16);
+        else GS_APPLY_FRAG(GS_BF16);
+#undef GS_APPLY_FRAG
+        GS_CHECK_LAUNCH("gs_bn_act_apply_split_lo");
+        return GS_OK;
+    }
 #define GS_APPLY_SPLIT(DT)                                                                         \
     do {                                                                                           \
         if (pool) {                                                                                \
@@ -951,7 +1199,7 @@ extern "C" int gs_bn_act_apply_split_pool3d(const void* y_hi, const void* y_lo, 
 }
 
 static int head1x1_split_impl(const void* x_hi, const void* x_lo, const float* scale, const float* shift, int act, const float* w,
-                              const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int dtype, void* stream);
+                              const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int dtype, void* stream, int lo_layout = 0);
 // the head on a CONV OUTPUT pair with BatchNorm + activation on the load path: the last activation pair is never stored
 extern "C" int gs_head1x1_bn_fwd_split(const void* y_hi, const void* y_lo, const float* scale, const float* shift, int act,
                                        const float* w, const float* bias, float* logits, int N, int H, int W, int Cin, int Cout,
@@ -960,13 +1208,24 @@ extern "C" int gs_head1x1_bn_fwd_split(const void* y_hi, const void* y_lo, const
     GS_CHECK_ARG(act == GS_ACT_NONE || act == GS_ACT_RELU || act == GS_ACT_LEAKY02, "gs_head1x1_bn_fwd_split: activation %d", act);
     return head1x1_split_impl(y_hi, y_lo, scale, shift, act, w, bias, logits, N, H, W, Cin, Cout, dtype, stream);
 }
+// the same with the layout of y_lo stated (0 dense, 1 fragment order: H % 16 == 0, W % 32 == 0, 1..4 classes)
+extern "C" int gs_head1x1_bn_fwd_split_lo(const void* y_hi, const void* y_lo, const float* scale, const float* shift, int act,
+                                          const float* w, const float* bias, float* logits, int N, int H, int W, int Cin, int Cout,
+                                          int dtype, int lo_layout, void* stream) {
+    GS_CHECK_ARG(scale && shift, "gs_head1x1_bn_fwd_split_lo: scale / shift are NULL");
+    GS_CHECK_ARG(act == GS_ACT_NONE || act == GS_ACT_RELU || act == GS_ACT_LEAKY02, "gs_head1x1_bn_fwd_split_lo: activation %d", act);
+    GS_CHECK_ARG(lo_layout == 0 || lo_layout == 1, "gs_head1x1_bn_fwd_split_lo: lo_layout must be 0 (dense) or 1 (fragment order)");
+    return head1x1_split_impl(y_hi, y_lo, scale, shift, act, w, bias, logits, N, H, W, Cin, Cout, dtype, stream, lo_layout);
+}
 extern "C" int gs_head1x1_fwd_split(const void* x_hi, const void* x_lo, const float* w, const float* bias, float* y, int N,
                                     int H, int W, int Cin, int Cout, int dtype, void* stream) {
     return head1x1_split_impl(x_hi, x_lo, nullptr, nullptr, GS_ACT_NONE, w, bias, y, N, H, W, Cin, Cout, dtype, stream);
 }
 static int head1x1_split_impl(const void* x_hi, const void* x_lo, const float* scale, const float* shift, int act, const float* w,
-                              const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int dtype, void* stream) {
+                              const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int dtype, void* stream, int lo_layout) {
     GS_CHECK_ARG(x_hi && x_lo && w && y && N > 0 && H > 0 && W > 0, "gs_head1x1_fwd_split: bad arguments");
+    GS_CHECK_ARG(lo_layout == 0 || (H % 16 == 0 && W % 32 == 0 && Cout <= 4),
+                 "gs_head1x1_bn_fwd_split_lo: a fragment-order lo plane needs H %% 16 == 0, W %% 32 == 0 and 1..4 classes");
     GS_CHECK_ARG(Cin == 64 && Cout >= 1 && Cout <= 64, "gs_head1x1_fwd_split: Cin must be 64 and Cout 1..64");
     GS_CHECK_ARG((((uintptr_t)x_hi | (uintptr_t)x_lo) & 15) == 0, "gs_head1x1_fwd_split: x_hi / x_lo must be 16-byte aligned");
     GS_CHECK_ARG((int64_t)N * H * W + 256 < 2147483647LL, "gs_head1x1_fwd_split: too many pixels");
@@ -983,6 +1242,14 @@ static int head1x1_split_impl(const void* x_hi, const void* x_lo, const float* s
         if (dtype == GS_F16) head1x1_wide_split_kernel<GS_F16><<<(int)wb, 256, 0, s>>>(a);
         else head1x1_wide_split_kernel<GS_BF16><<<(int)wb, 256, 0, s>>>(a);
         GS_CHECK_LAUNCH("gs_head1x1_fwd_split");
+        return GS_OK;
+    }
+    if (lo_layout == 1) {                                  // one wave per 32-pixel row, four per block
+        int64_t fb = cdiv64((int64_t)N * H * (W / 32), 4);
+        if (fb > 8192) fb = 8192;
+        if (dtype == GS_F16) head1x1_split_frag_kernel<GS_F16><<<(int)fb, 256, 0, s>>>(a, H, W);
+        else head1x1_split_frag_kernel<GS_BF16><<<(int)fb, 256, 0, s>>>(a, H, W);
+        GS_CHECK_LAUNCH("gs_head1x1_bn_fwd_split_lo");
         return GS_OK;
     }
     if (dtype == GS_F16) head1x1_split_kernel<GS_F16><<<(int)hb, 256, 0, s>>>(a);
@@ -1035,6 +1302,32 @@ extern "C" int gs_head1x1_labels(const void* x_hi, const void* x_lo, const float
         else head1x1_split_kernel<GS_BF16, true><<<(int)hb, 256, 0, s>>>(a);
     }
     GS_CHECK_LAUNCH("gs_head1x1_labels");
+    return GS_OK;
+}
+
+// The same on a conv-output pair [N,H,W,64] whose lo plane is in the stated layout (0 dense, 1 fragment order: H % 16 == 0,
+// W % 32 == 0, 1..4 classes); labels [N,H,W]
+extern "C" int gs_head1x1_labels_lo(const void* x_hi, const void* x_lo, const float* scale, const float* shift, int act, const float* w,
+                                    const float* bias, uint8_t* labels, int N, int H, int W, int ncls, int dtype, int lo_layout,
+                                    void* stream) {
+    GS_CHECK_ARG(N > 0 && H > 0 && W > 0 && (lo_layout == 0 || lo_layout == 1), "gs_head1x1_labels_lo: bad arguments");
+    if (lo_layout == 0) return gs_head1x1_labels(x_hi, x_lo, scale, shift, act, w, bias, labels, (int64_t)N * H * W, ncls, dtype, stream);
+    GS_CHECK_ARG(x_hi && x_lo && w && labels, "gs_head1x1_labels_lo: bad arguments");
+    GS_CHECK_ARG(ncls >= 1 && ncls <= 4 && H % 16 == 0 && W % 32 == 0,
+                 "gs_head1x1_labels_lo: a fragment-order lo plane needs H %% 16 == 0, W %% 32 == 0 and 1..4 classes");
+    GS_CHECK_ARG((((uintptr_t)x_hi | (uintptr_t)x_lo) & 15) == 0, "gs_head1x1_labels_lo: x_hi / x_lo must be 16-byte aligned");
+    GS_CHECK_ARG((int64_t)N * H * W + 8192 * 256 < 2147483647LL, "gs_head1x1_labels_lo: too many pixels");
+    GS_CHECK_ARG(dtype == GS_F16 || dtype == GS_BF16, "gs_head1x1_labels_lo: bad dtype");
+    GS_CHECK_ARG((scale == nullptr) == (shift == nullptr), "gs_head1x1_labels_lo: scale / shift must both be given or NULL");
+    GS_CHECK_ARG(act == GS_ACT_NONE || act == GS_ACT_RELU || act == GS_ACT_LEAKY02, "gs_head1x1_labels_lo: activation %d", act);
+    HeadSArgs a{(const unsigned short*)x_hi, (const unsigned short*)x_lo, w, bias, nullptr, N, H * W, ncls};
+    a.scale = scale; a.shift = shift; a.act = act; a.lab = labels;
+    int64_t fb = cdiv64((int64_t)N * H * (W / 32), 4);
+    if (fb > 8192) fb = 8192;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == GS_F16) head1x1_split_frag_kernel<GS_F16, true><<<(int)fb, 256, 0, s>>>(a, H, W);
+    else head1x1_split_frag_kernel<GS_BF16, true><<<(int)fb, 256, 0, s>>>(a, H, W);
+    GS_CHECK_LAUNCH("gs_head1x1_labels_lo");
     return GS_OK;
 }
 

@@ -1592,12 +1592,27 @@ def pack_weight_segs(items):
     _lib.call("gs_pack_weight_segs", len(items), descs, dt_code(ref), _stream())
 
 
+LO_DENSE, LO_FRAGMENT = 0, 1
+
+
+def conv3x3_pair_lo_layout(N, H, W, K, Cout) -> int:
+    """Layout of the conv-output lo plane a conv3x3_segs launch of these dimensions (K = its K extent) may use: LO_DENSE (NHWC) or
+    LO_FRAGMENT (as the lanes of the 8-wave LDS-DMA form hold the tile, include/gsseg.h) -- only for launches with statistics, no
+    bias, no activation and a dense output.  Ask once per stage and pass the answer to the conv AND to the reader of y_lo."""
+    return int(_lib.load().gs_conv3x3_pair_lo_layout(N, H, W, K, Cout))
+
+
+def pair_lo_set_layout(mode: int = -1) -> None:
+    """Process-wide: -1 automatic, 0 dense lo planes everywhere (tests and A/B runs; restore -1)."""
+    _lib.call("gs_pair_lo_set_layout", int(mode))
+
+
 def conv3x3_segs(x, w, y_hi, y_lo, N, H, W, K, wrap, Cin, Cout, in_stride, in_coff=0, out_stride=None, out_coff=0,
-                 bias=None, bn_partials=None, act=ACT_NONE, taps=TAPS3_FWD):
+                 bias=None, bn_partials=None, act=ACT_NONE, taps=TAPS3_FWD, lo_layout=LO_DENSE):
     """3x3/s1/p1 convolution of the pair forward with a free choice of MFMA segments: the K extent (a multiple of 64,
     wrap <= K <= 2*wrap) runs over the input channels [in_coff, in_coff + wrap) of x and wraps to in_coff once; w is the
     matching pack_weight_segs pack [9][Cout][K]; Cin = the layer's channels (for the FLOP count only).  Result: pair
-    y_hi / y_lo."""
+    y_hi / y_lo; lo_layout = LO_FRAGMENT (conv3x3_pair_lo_layout): y_lo is a plain buffer in fragment order."""
     _dev(x)
     _f32(bias, "bias"); _f32(bn_partials, "bn_partials")
     if not (x.dtype == w.dtype == y_hi.dtype == y_lo.dtype):
@@ -1608,9 +1623,9 @@ def conv3x3_segs(x, w, y_hi, y_lo, N, H, W, K, wrap, Cin, Cout, in_stride, in_co
         raise ValueError("conv3x3_segs: bn_partials too small (conv3x3_stat_rows(pair=True) rows of [2][Cout])")
     dy, dx = _tap_arrays(taps)
     ev = TIMER.start() if TIMER is not None else None
-    _lib.call("gs_conv3x3_precise", _p(x), _p(w), _p(y_hi), _p(y_lo), _p(bias), _p(bn_partials), N, H, W, K,
+    _lib.call("gs_conv3x3_precise_lo", _p(x), _p(w), _p(y_hi), _p(y_lo), _p(bias), _p(bn_partials), N, H, W, K,
               in_stride, in_coff, wrap, Cout, Cout if out_stride is None else out_stride, out_coff, dy, dx, act,
-              dt_code(x), _stream())
+              dt_code(x), int(lo_layout), _stream())
     if ev is not None:                       # algorithmic work of the convolution (the kernel executes K / Cin times the MFMAs)
         TIMER.stop("conv3x3_halo_precise", ev, 2.0 * N * H * W * Cout * 9 * Cin,
                    2.0 * (N * H * W * 2 * (Cin + Cout) + 9 * K * Cout))
@@ -1720,14 +1735,16 @@ def conv_widecin_fwd_split(x, w, y_hi, y_lo, bn_partials=None):
     _lib.check(rc, "gs_conv_widecin_fwd_split")
 
 
-def bn_act_apply_split(y_hi, y_lo, scale, shift, act, z_hi, z_lo, z_stride, z_coff, zp_hi=None, zp_lo=None, zp_stride=0):
-    """z pair = act(scale * (y_hi + y_lo) + shift); y_hi / y_lo dense [N,H,W,C]; optional 2x2 max-pooled pair."""
+def bn_act_apply_split(y_hi, y_lo, scale, shift, act, z_hi, z_lo, z_stride, z_coff, zp_hi=None, zp_lo=None, zp_stride=0,
+                       lo_layout=LO_DENSE):
+    """z pair = act(scale * (y_hi + y_lo) + shift); y_hi / y_lo dense [N,H,W,C] (lo_layout = LO_FRAGMENT: y_lo as conv3x3_segs wrote
+    it in that layout); optional 2x2 max-pooled pair."""
     N, H, W, C = y_hi.shape
     if not (y_hi.is_contiguous() and y_lo.is_contiguous()) or y_lo.shape != y_hi.shape:
         raise ValueError("bn_act_apply_split: y_hi / y_lo must be dense NHWC of one shape")
     _f32(scale, "scale"); _f32(shift, "shift")
-    _lib.call("gs_bn_act_apply_split", _p(y_hi), _p(y_lo), _p(scale), _p(shift), act, _p(z_hi), _p(z_lo), z_stride, z_coff,
-              _p(zp_hi), _p(zp_lo), zp_stride, N, H, W, C, dt_code(y_hi), _stream())
+    _lib.call("gs_bn_act_apply_split_lo", _p(y_hi), _p(y_lo), _p(scale), _p(shift), act, _p(z_hi), _p(z_lo), z_stride, z_coff,
+              _p(zp_hi), _p(zp_lo), zp_stride, N, H, W, C, dt_code(y_hi), int(lo_layout), _stream())
 
 
 def bn_act_apply_split_pool3d(y_hi, y_lo, scale, shift, act, z_hi, z_lo, z_stride, z_coff, zp_hi, zp_lo, zp_stride, NB, D, H, W):
@@ -1741,8 +1758,9 @@ def bn_act_apply_split_pool3d(y_hi, y_lo, scale, shift, act, z_hi, z_lo, z_strid
               _p(zp_hi), _p(zp_lo), zp_stride, NB, D, H, W, C, dt_code(y_hi), _stream())
 
 
-def head1x1_bn_fwd_split(y_hi, y_lo, scale, shift, act, w, bias, logits):
-    """OutConv 1x1 on act(scale * (y_hi + y_lo) + shift) of a dense conv-output pair [N,H,W,64] -> fp32 NCHW logits."""
+def head1x1_bn_fwd_split(y_hi, y_lo, scale, shift, act, w, bias, logits, lo_layout=LO_DENSE):
+    """OutConv 1x1 on act(scale * (y_hi + y_lo) + shift) of a dense conv-output pair [N,H,W,64] -> fp32 NCHW logits
+    (lo_layout = LO_FRAGMENT: y_lo in fragment order, 1..4 classes)."""
     _dev(y_hi)
     _f32(scale, "scale"); _f32(shift, "shift"); _f32(w, "w"); _f32(bias, "bias"); _f32(logits, "logits")
     N, H, W, C = y_hi.shape
@@ -1751,8 +1769,8 @@ def head1x1_bn_fwd_split(y_hi, y_lo, scale, shift, act, w, bias, logits):
             or not 1 <= ncls <= 64 or (bias is not None and bias.numel() != ncls)
             or not (y_hi.is_contiguous() and y_lo.is_contiguous() and logits.is_contiguous())):
         raise ValueError("head1x1_bn_fwd_split: y pair [N,H,W,64] dense, logits [N,ncls,H,W] with 1..64 classes, w [ncls,64]")
-    _lib.call("gs_head1x1_bn_fwd_split", _p(y_hi), _p(y_lo), _p(scale), _p(shift), act, _p(w), _p(bias), _p(logits), N, H, W, 64,
-              ncls, dt_code(y_hi), _stream())
+    _lib.call("gs_head1x1_bn_fwd_split_lo", _p(y_hi), _p(y_lo), _p(scale), _p(shift), act, _p(w), _p(bias), _p(logits), N, H, W, 64,
+              ncls, dt_code(y_hi), int(lo_layout), _stream())
 
 
 def head1x1_fwd_split(x_hi, x_lo, w, bias, y):
@@ -1782,7 +1800,7 @@ def head1x1_wide_fwd(x, w, bias, y):
     _lib.call("gs_head1x1_wide_fwd", _p(x), _p(w), _p(bias), _p(y), N, H, W, ncls, dt_code(x), _stream())
 
 
-def head1x1_labels(x_hi, x_lo, w, bias, labels, scale=None, shift=None, act=ACT_NONE):
+def head1x1_labels(x_hi, x_lo, w, bias, labels, scale=None, shift=None, act=ACT_NONE, lo_layout=LO_DENSE):
     """Labels straight from the pair head (GenSeg-3D/train_unet.py:39, unet/evaluate.py:29-40): x_hi / x_lo dense pair [..., 64]
     (scale / shift / act: BatchNorm + activation on the load path, x = a conv-output pair), w [ncls,64], 1..64 classes -> labels uint8,
     one per pixel in the order of the input pixels.  One class: sigmoid > 0.5; several: the first maximum.  No logits are stored."""
@@ -1795,6 +1813,12 @@ def head1x1_labels(x_hi, x_lo, w, bias, labels, scale=None, shift=None, act=ACT_
             or not w.is_contiguous() or (bias is not None and bias.numel() != ncls) or (scale is None) != (shift is None)):
         raise ValueError("head1x1_labels: x pair [...,64] dense of one 16-bit dtype, labels uint8 with one byte per pixel, w [ncls,64], "
                          "bias [ncls], scale / shift together")
+    if lo_layout != LO_DENSE:                # x_lo in fragment order: the image dimensions matter ([N,H,W,64] pair, 1..4 classes)
+        if x_hi.dim() != 4:
+            raise ValueError("head1x1_labels: a fragment-order lo plane needs the pair as [N,H,W,64]")
+        _lib.call("gs_head1x1_labels_lo", _p(x_hi), _p(x_lo), _p(scale), _p(shift), act, _p(w), _p(bias), _p(labels), x_hi.shape[0],
+                  x_hi.shape[1], x_hi.shape[2], ncls, dt_code(x_hi), int(lo_layout), _stream())
+        return
     _lib.call("gs_head1x1_labels", _p(x_hi), _p(x_lo), _p(scale), _p(shift), act, _p(w), _p(bias), _p(labels), M, ncls,
               dt_code(x_hi), _stream())
 

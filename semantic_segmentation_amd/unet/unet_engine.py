@@ -725,6 +725,7 @@ class UNetEngine(ParamIndex):
                                             N, h, w, cout)
                 return None
             y_hi, y_lo = empty(N, h, w, cout), empty(N, h, w, cout)
+            lo_layout = ops.LO_DENSE                        # of y_lo: asked once, handed to the conv and to the plane's one reader
             if wide_img:
                 # the conv-output pair and the statistics from the fp32 image and weights: no 16-bit image in the forward
                 ops.conv_widecin_fwd_split(inp, wparam.detach().contiguous(), y_hi, y_lo, partials)
@@ -742,8 +743,10 @@ class UNetEngine(ParamIndex):
                 ops.conv3x3_q8(inp, qpack, wexp, y_hi, y_lo, N, h, w, cin, cout, in_stride=2 * cin, bn_partials=partials)
             else:
                 _, K, wrap = _segs(plan[short], cin, self._lo_len(short, plan, cin))
+                if partials is not None and want_lo != 2 and zp_want_lo != 2:      # (the q-plane apply pass reads a dense lo plane)
+                    lo_layout = ops.conv3x3_pair_lo_layout(N, h, w, K, cout)
                 ops.conv3x3_segs(inp, self._seg_pack(wkey), y_hi, y_lo, N, h, w, K, wrap, cin, cout, in_stride=2 * cin,
-                                 bn_partials=partials)
+                                 bn_partials=partials, lo_layout=lo_layout)
             coef = bn_coeffs(self.submodule(bnkey), partials, ntiles, cout, N * h * w, training, dev, nbt_pending)[0]
             rec.y, rec.coef = y_hi, coef
             if wide_img:
@@ -753,7 +756,7 @@ class UNetEngine(ParamIndex):
             if need_grad:
                 recs.append(rec)
             if to_head:
-                return rec, y_lo
+                return rec, y_lo, lo_layout
             zp_hi = zp if zp is not None else None
             zp_lo = zp[..., zp.shape[3] // 2:] if (zp is not None and zp_want_lo) else None
             if want_lo == 2 or zp_want_lo == 2:
@@ -761,7 +764,7 @@ class UNetEngine(ParamIndex):
                                           zp_want_lo == 2, 0 if zp is None else zp.shape[3])
             else:
                 ops.bn_act_apply_split(y_hi, y_lo, coef[0], coef[1], ACT_RELU, zbuf, z_lo, z_stride, 0, zp_hi, zp_lo,
-                                       0 if zp is None else zp.shape[3])
+                                       0 if zp is None else zp.shape[3], lo_layout=lo_layout)
             return rec
 
         def reads_lo(st):
@@ -861,14 +864,14 @@ class UNetEngine(ParamIndex):
                 z_last = zl_hi
             elif not full and FUSED_HEAD_FWD and cout3 == 64 and net.n_classes <= 4:
                 # last stage: its activation has one reader, the head, which applies BatchNorm + ReLU on its own load path
-                last_rec, y_lo_last = stage(prefix + ".conv", 3, zmid, cmid, cout3, H2, W2, None, 0, False, to_head=True)
+                last_rec, y_lo_last, lo_last = stage(prefix + ".conv", 3, zmid, cmid, cout3, H2, W2, None, 0, False, to_head=True)
             else:                                  # last stage: two dense planes (the head and its backward read dense tensors)
                 zl = empty(2, N, H2, W2, cout3)
                 zl_hi, zl_lo = zl[0], zl[1]
                 last_rec = None
                 st_rec = stage(prefix + ".conv", 3, zmid, cmid, cout3, H2, W2, None, 0, False, to_head=True)
                 ops.bn_act_apply_split(st_rec[0].y, st_rec[1], st_rec[0].coef[0], st_rec[0].coef[1], ACT_RELU, zl_hi, zl_lo,
-                                       cout3, 0)
+                                       cout3, 0, lo_layout=st_rec[2])
                 z_last = zl_hi
 
         if labels:
@@ -877,7 +880,7 @@ class UNetEngine(ParamIndex):
             wout = params["outc.conv.weight"].detach().reshape(net.n_classes, 64).contiguous()
             if z_last is None:
                 ops.head1x1_labels(last_rec.y, y_lo_last, wout, params["outc.conv.bias"].detach(), lab, last_rec.coef[0],
-                                   last_rec.coef[1], ACT_RELU)
+                                   last_rec.coef[1], ACT_RELU, lo_layout=lo_last)
             else:
                 ops.head1x1_labels(zl_hi, zl_lo, wout, params["outc.conv.bias"].detach(), lab)
             _flush_nbt(nbt_pending)
@@ -885,7 +888,8 @@ class UNetEngine(ParamIndex):
         logits = empty(N, net.n_classes, H, W, dtype=torch.float32)
         if z_last is None:
             ops.head1x1_bn_fwd_split(last_rec.y, y_lo_last, last_rec.coef[0], last_rec.coef[1], ACT_RELU,
-                                     params["outc.conv.weight"].detach().contiguous(), params["outc.conv.bias"].detach(), logits)
+                                     params["outc.conv.weight"].detach().contiguous(), params["outc.conv.bias"].detach(), logits,
+                                     lo_layout=lo_last)
         else:
             ops.head1x1_fwd_split(zl_hi, zl_lo, params["outc.conv.weight"].detach().contiguous(),
                                   params["outc.conv.bias"].detach(), logits)

@@ -21,3 +21,22 @@ for name, H, Cin, Cout in [("inc.3 64->64@256", 256, 64, 64), ("u4.0 128->64@256
     for w in (0, 5):
         ph = allw[w].tolist()[:6]; tot = sum(ph)
         print(f"{name:20s} wave{w} cycles {int(tot):8d}  " + "  ".join(f"{n} {100*v/tot:4.1f}%" for n, v in zip(names, ph)), flush=True)
+
+# the pair form (8 waves, "xw" segments: K = 3 * 64 over the [hi | lo] input) with the dense and the fragment-order lo plane
+# (GSSEG_PAIR_LO_DEFER=0: the fragment-order launch keeps the immediate hi epilogue); "boundary" is the epilogue / conversion
+if hasattr(ops, "conv3x3_pair_lo_layout"):
+    H, cin, K, wrap, Cout = 256, 64, 192, 128, 64
+    x = (0.7 * torch.randn(N, H, H, 2 * cin, device=dev)).to(dt); pack = (0.05 * torch.randn(9, Cout, K, device=dev)).to(dt)
+    y_hi = torch.empty(N, H, H, Cout, device=dev, dtype=dt); y_lo = torch.empty_like(y_hi)
+    for tag, mode in (("dense lo", 0), ("fragment lo", -1)):
+        ops.pair_lo_set_layout(mode)
+        lay = ops.conv3x3_pair_lo_layout(N, H, H, K, Cout)
+        part = torch.zeros(max(ops.bn_partials_numel(ops.conv3x3_mtiles(N, H, H, Cout), Cout), 301 * 2 * Cout + 64), device=dev)
+        for _ in range(3):
+            ops.conv3x3_segs(x, pack, y_hi, y_lo, N, H, H, K, wrap, cin, Cout, in_stride=2 * cin, bn_partials=part, lo_layout=lay)
+        torch.cuda.synchronize()
+        allw = part[300 * 2 * Cout: 300 * 2 * Cout + 64].cpu().view(8, 8)
+        for w in (0, 5):
+            ph = allw[w].tolist()[:6]; tot = sum(ph)
+            print(f"pair 64->64@256 {tag:12s} wave{w} cycles {int(tot):8d}  " + "  ".join(f"{n} {100*v/tot:4.1f}%" for n, v in zip(names, ph)), flush=True)
+    ops.pair_lo_set_layout(-1)
