@@ -938,6 +938,45 @@ int64_t gs_conv3d_head_bwd_ws_floats(int N, int OD, int OH, int OW, int Cin, int
 int gs_conv3d_head_bwd(const void* x, const float* w, const float* dl, void* dz, float* dw, float* db, float* ws, int N, int D, int H,
                        int W, int Cin, int OD, int OH, int OW, int k, int pad, float gscale, int dtype, void* stream);
 
+/* The two operators of the 3-D Pix2Pix generator (csrc/cell3d.hip; GenSeg-3D/models/networks.py:570-601 MixedOp_conv / Cell_conv over
+ * architecture_pix2pix/operations.py:41-66, and networks.py:50-81 LinearAdditiveUpsample).
+ *
+ * Mixed cell: sum_j softmax3[j] Conv3d_j(x), (k, s, p) = (4,2,1), (6,2,2), (8,2,3), is one 8x8x8 / stride 2 / pad 3 conv (k4 at
+ * offset 2, k6 at offset 1).  On the parity-gathered tensor x'[a,(pz,py,px,c)] = x[2a+pz-1, 2i+py-1, 2j+px-1, c] (zero outside the
+ * volume; GD = D/2 + 1 entries per axis, [N*GD,GH,GW,8 Cin], dense) it is a stride-1 conv of 4x4x4 taps dt = -1..2 per axis
+ * (k = 2 dt + p + 2), which gs_conv_igemm / gs_conv_wgrad_slabs run; the data gradient goes through the eight sub-voxel classes of
+ * the stride-2 conv.  C_in is 1..4 (an fp32 image volume) or a multiple of 8, C_out a multiple of 8 (else GS_EUNSUPPORTED); every
+ * spatial size >= 2; null / misaligned pointers, bad dtype, strides or boxes are GS_EINVAL.  All checks come before any launch.
+ * gs_cell3d_gather: exactly one source -- x16 16-bit [N*D,H,W,*] (in_pix_stride, in_coff; C_in % 8 == 0) or x32 fp32 NCDHW
+ *   [N,C_in,D,H,W] with C_in 1..4, rounded once to 16 bits -- to out = x' (16-byte stores).  Samples never mix.
+ * gs_cell3d_merge_pack: w4 / w6 / w8 fp32 [C_out][C_in][k][k][k], softmax3 fp32 [3] on the device; (sm0 w4 + sm1 w6) + sm2 w8 in
+ *   fp32, rounded once.  pack_fwd [nd0*nd1*nd2][C_out][8 C_in] in gathered channel order over the tap box dt0[i] .. dt0[i]+nd[i]-1
+ *   (inside -1..2); pack_dgrad [nk0*nk1*nk2][cin_pad][C_out] over the tap box k0[i] .. k0[i]+nk[i]-1 (inside 0..7), rows
+ *   ci >= C_in zero.  Either pack may be NULL (its box is then not read).  The boxes are host arrays of 3 ints.
+ * gs_cell3d_split_wgrad: dwm fp32 [nd taps][C_out][8 C_in] (the weight gradient over the gathered geometry; taps outside the box
+ *   have gradient zero) -> dw_j = gscale * softmax3[j] * centred crop (each overwritten, the modules' layout) and
+ *   dots3[j] = gscale * <dwm, embed(w_j)> (overwritten) through per-block partials in ws (gs_cell3d_split_wgrad_ws_floats floats)
+ *   added in block order: no atomics, two runs give equal bits. */
+int gs_cell3d_gather(const void* x16, const float* x32, void* out, int N, int D, int H, int W, int Cin, int in_pix_stride, int in_coff,
+                     int dtype, void* stream);
+int gs_cell3d_merge_pack(const float* w4, const float* w6, const float* w8, const float* softmax3, void* pack_fwd, void* pack_dgrad,
+                         int Cin, int Cout, int cin_pad, const int* dt0, const int* nd, const int* k0, const int* nk, int dtype,
+                         void* stream);
+int64_t gs_cell3d_split_wgrad_ws_floats(int Cin, int Cout);
+int gs_cell3d_split_wgrad(const float* dwm, const float* w4, const float* w6, const float* w8, const float* softmax3, float gscale,
+                          float* dw4, float* dw6, float* dw8, float* dots3, float* ws, int Cin, int Cout, const int* dt0, const int* nd,
+                          void* stream);
+
+/* LinearAdditiveUpsample(scale_factor 2, n_splits 4, threed) on 16-bit depth-slice stacks: x [N*D,H,W,C] (stride, offset) ->
+ * y [N*2D,2H,2W,C/4] (stride, offset), y[c'] = trilinear_x2(sum_{i<4} x[4c'+i]) with align_corners=False (per axis: output 2i =
+ * 0.25 x[i-1] + 0.75 x[i], output 2i+1 = 0.75 x[i] + 0.25 x[i+1], indices clamped), fp32 arithmetic, one rounding.  The backward is
+ * the exact adjoint in gather form (per axis the outputs 2i-1 .. 2i+2, the clamp's share folded onto the edge): dx[4c'+i] is the
+ * same value for the four i; fixed order, no atomics.  C % 32 == 0 (else GS_EUNSUPPORTED); strides / offsets % 8 == 0. */
+int gs_upsample_add3d_fwd(const void* x, void* y, int N, int D, int H, int W, int C, int in_pix_stride, int in_coff, int out_pix_stride,
+                          int out_coff, int dtype, void* stream);
+int gs_upsample_add3d_bwd(const void* dy, void* dx, int N, int D, int H, int W, int C, int dy_pix_stride, int dy_coff, int dx_pix_stride,
+                          int dx_coff, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2115,3 +2115,154 @@ def conv3d_head_bwd(x, w, dl, dz, dw, db, k, pad, gscale=1.0, ws=None):
             raise ValueError("conv3d_head_bwd: ws needs gs_conv3d_head_bwd_ws_floats floats")
     _head3d_call("gs_conv3d_head_bwd", Cin, k, pad, _p(x), _p(w), _p(dl), _p(dz), _p(dw), _p(db), _p(ws), N, D, H, W, Cin, OD, OH, OW,
                  k, pad, float(gscale), dt_code(ref), _stream())
+
+
+# ---------------------------------------------------------------------------- 3-D Pix2Pix cells (csrc/cell3d.hip)
+# The mixed stride-2 Conv3d cell as a 64-tap stride-1 conv over the parity-gathered volume, and the linear additive upsample.
+def cell3d_gathered_size(d: int) -> int:
+    """entries per axis of the gathered tensor x'[a] = x[2a + p - 1]: ceil((d + 1) / 2)"""
+    return d // 2 + 1
+
+
+def cell3d_reachable_taps(d: int):
+    """taps kz of the 8 / stride 2 / pad 3 conv that meet data on an axis of d entries: some output o has 0 <= 2o + kz - 3 < d"""
+    return [kz for kz in range(8) if any(0 <= 2 * o + kz - 3 < d for o in range(d // 2))]
+
+
+def cell3d_boxes(D: int, H: int, W: int, full: bool = False):
+    """(dt0, nd, k0, nk): per axis, the box of gathered taps dt = (k >> 1) - 1 in -1..2 and the box of taps k in 0..7 that can meet
+    data (full=True: all of them).  Taps outside never multiply anything but padding; packs and launches leave them out."""
+    dt0, nd, k0, nk = [], [], [], []
+    for d in (D, H, W):
+        ks = list(range(8)) if full else cell3d_reachable_taps(d)
+        if not ks:
+            raise NotImplementedError("mixed Conv3d cell: every spatial size must be >= 2")
+        lo, hi = (ks[0] >> 1) - 1, (ks[-1] >> 1) - 1
+        dt0.append(lo); nd.append(hi - lo + 1); k0.append(ks[0]); nk.append(len(ks))
+    return tuple(dt0), tuple(nd), tuple(k0), tuple(nk)
+
+
+def _i3(v):
+    return (ctypes.c_int32 * 3)(*[int(i) for i in v])
+
+
+def _cell3d_call(name, *args):
+    rc = getattr(_lib.load(), name)(*args)
+    if rc == _lib.GS_EUNSUPPORTED:
+        msg = _lib.load().gs_last_error()
+        raise NotImplementedError(msg.decode() if msg else name)
+    _lib.check(rc, name)
+
+
+def geom_cell3d_fwd(N, D, H, W, Cin, Cout, dt0, nd, **kw) -> GsConvGeom:
+    """the mixed cell over the gathered tensor x' [N*GD,GH,GW,8 Cin]: stride 1, taps dt of the box in (z, y, x) row-major order =
+    the order of the forward pack and of the weight gradient [taps][Cout][8 Cin]"""
+    GD, GH, GW = cell3d_gathered_size(D), cell3d_gathered_size(H), cell3d_gathered_size(W)
+    OD, OH, OW = D // 2, H // 2, W // 2
+    t3 = [(dt0[0] + a, dt0[1] + b, dt0[2] + c) for a in range(nd[0]) for b in range(nd[1]) for c in range(nd[2])]
+    return make_geom(N, GH, GW, 8 * Cin, OH, OW, Cout, OH, OW, [(y, x) for (_, y, x) in t3], tap_dz=[z for (z, _, _) in t3],
+                     Dg=OD, Din=GD, Dout=OD, **kw)
+
+
+def geom_cell3d_dgrad_class(N, D, H, W, Cin, Cout, k0, nk, pz, py, px, **kw):
+    """geom_conv3d_s2_dgrad_class(k=8, pad=3) restricted to the tap box k0 .. k0 + nk of a compact [nk taps][Cin][Cout] pack; None
+    when no tap of the class lies in the box (the class's voxels then receive no gradient: the caller zero-fills dx)"""
+    OD, OH, OW = D // 2, H // 2, W // 2
+    sel = [(kz, ky, kx) for kz in range(k0[0], k0[0] + nk[0]) for ky in range(k0[1], k0[1] + nk[1]) for kx in range(k0[2], k0[2] + nk[2])
+           if (pz + 3 - kz) % 2 == 0 and (py + 3 - ky) % 2 == 0 and (px + 3 - kx) % 2 == 0]
+    dg, ihg, iwg = (D - pz + 1) // 2, (H - py + 1) // 2, (W - px + 1) // 2
+    if not sel or dg <= 0 or ihg <= 0 or iwg <= 0:
+        return None
+    taps = [((py + 3 - ky) // 2, (px + 3 - kx) // 2) for (_, ky, kx) in sel]
+    dz = [(pz + 3 - kz) // 2 for (kz, _, _) in sel]
+    slots = [((kz - k0[0]) * nk[1] + ky - k0[1]) * nk[2] + kx - k0[2] for (kz, ky, kx) in sel]
+    return make_geom(N, OH, OW, Cout, ihg, iwg, Cin, H, W, taps, osy=2, osx=2, ooy=py, oox=px, tap_w=slots, tap_dz=dz,
+                     Dg=dg, Din=OD, Dout=D, osz=2, ooz=pz, **kw)
+
+
+def cell3d_gather(src, out, N, D, H, W, Cin, in_stride=None, in_coff=0):
+    """src: 16-bit [N*D,H,W,*] (Cin % 8 == 0, channel slice in_coff .. in_coff + Cin of in_stride) or an fp32 NCDHW volume with Cin
+    1..4 -> out 16-bit [N*GD,GH,GW,8 Cin], out[a,(pz,py,px,c)] = src[2a+pz-1, 2i+py-1, 2j+px-1, c], zero outside the volume."""
+    _dev(src)
+    need = N * cell3d_gathered_size(D) * cell3d_gathered_size(H) * cell3d_gathered_size(W) * 8 * Cin
+    if out.numel() != need or not out.is_contiguous():
+        raise ValueError("cell3d_gather: out must be dense [N*GD,GH,GW,8*Cin]")
+    if src.dtype == torch.float32:
+        if tuple(src.shape) != (N, Cin, D, H, W) or not src.is_contiguous():
+            raise ValueError("cell3d_gather: an fp32 source is a contiguous [N,Cin,D,H,W] volume")
+        _cell3d_call("gs_cell3d_gather", None, _p(src), _p(out), N, D, H, W, Cin, 0, 0, dt_code(out), _stream())
+        return
+    if src.dtype != out.dtype:
+        raise TypeError("cell3d_gather: a 16-bit source and out must share one dtype")
+    stride = Cin if in_stride is None else in_stride
+    if src.numel() < N * D * H * W * stride:
+        raise ValueError("cell3d_gather: the source is smaller than [N*D,H,W,in_stride]")
+    _cell3d_call("gs_cell3d_gather", _p(src), None, _p(out), N, D, H, W, Cin, stride, in_coff, dt_code(out), _stream())
+
+
+def cell3d_merge_pack(w4, w6, w8, softmax3, pack_fwd=None, pack_dgrad=None, dt0=(-1, -1, -1), nd=(4, 4, 4), k0=(0, 0, 0),
+                      nk=(8, 8, 8), cin_pad=None):
+    """(sm0 w4 + sm1 w6) + sm2 w8 (k4 embedded at offset 2, k6 at 1) -> pack_fwd [prod(nd)][Cout][8 Cin] and / or pack_dgrad
+    [prod(nk)][cin_pad][Cout], each over its tap box, rounded once."""
+    _dev(w8)
+    for n, t in (("w4", w4), ("w6", w6), ("w8", w8), ("softmax3", softmax3)):
+        _f32(t, n)
+    Cout, Cin = w8.shape[0], w8.shape[1]
+    if tuple(w4.shape) != (Cout, Cin, 4, 4, 4) or tuple(w6.shape) != (Cout, Cin, 6, 6, 6) or tuple(w8.shape) != (Cout, Cin, 8, 8, 8) \
+            or softmax3.numel() != 3:
+        raise ValueError("cell3d_merge_pack: w4 / w6 / w8 are [Cout][Cin][k][k][k] for k = 4, 6, 8; softmax3 has 3 entries")
+    cin_pad = (Cin + 7) // 8 * 8 if cin_pad is None else cin_pad
+    ref = pack_fwd if pack_fwd is not None else pack_dgrad
+    if ref is None:
+        raise ValueError("cell3d_merge_pack: no pack to write")
+    if pack_fwd is not None and (pack_fwd.numel() != nd[0] * nd[1] * nd[2] * Cout * 8 * Cin or not pack_fwd.is_contiguous()):
+        raise ValueError("cell3d_merge_pack: pack_fwd must be dense [prod(nd)][Cout][8*Cin]")
+    if pack_dgrad is not None and (pack_dgrad.numel() != nk[0] * nk[1] * nk[2] * cin_pad * Cout or not pack_dgrad.is_contiguous()
+                                   or pack_dgrad.dtype != ref.dtype):
+        raise ValueError("cell3d_merge_pack: pack_dgrad must be dense [prod(nk)][cin_pad][Cout] of the forward pack's dtype")
+    _cell3d_call("gs_cell3d_merge_pack", _p(w4), _p(w6), _p(w8), _p(softmax3), _p(pack_fwd), _p(pack_dgrad), Cin, Cout, cin_pad,
+                 _i3(dt0), _i3(nd), _i3(k0), _i3(nk), dt_code(ref), _stream())
+
+
+def cell3d_split_wgrad(dwm, w4, w6, w8, softmax3, gscale, dw4, dw6, dw8, dots3, dt0=(-1, -1, -1), nd=(4, 4, 4)):
+    """merged weight gradient fp32 [prod(nd)][Cout][8 Cin] -> dw4 / dw6 / dw8 (gscale * sm_j * centred crop) and
+    dots3[j] = gscale * <dwm, embed(w_j)>; deterministic."""
+    _dev(dwm)
+    for n, t in (("dwm", dwm), ("w4", w4), ("w6", w6), ("w8", w8), ("softmax3", softmax3), ("dw4", dw4), ("dw6", dw6), ("dw8", dw8),
+                 ("dots3", dots3)):
+        _f32(t, n)
+    Cout, Cin = w8.shape[0], w8.shape[1]
+    if dwm.numel() != nd[0] * nd[1] * nd[2] * Cout * 8 * Cin or dots3.numel() != 3 or any(
+            a.shape != b.shape for a, b in ((dw4, w4), (dw6, w6), (dw8, w8))):
+        raise ValueError("cell3d_split_wgrad: dwm is [prod(nd)][Cout][8*Cin]; dw_j has the shape of w_j; dots3 has 3 entries")
+    ws = torch.empty(max(int(_lib.load().gs_cell3d_split_wgrad_ws_floats(Cin, Cout)), 1), dtype=torch.float32, device=dwm.device)
+    _cell3d_call("gs_cell3d_split_wgrad", _p(dwm), _p(w4), _p(w6), _p(w8), _p(softmax3), float(gscale), _p(dw4), _p(dw6), _p(dw8),
+                 _p(dots3), _p(ws), Cin, Cout, _i3(dt0), _i3(nd), _stream())
+
+
+def upsample_add3d_fwd(x, y, N, D, H, W, C, in_stride=None, in_coff=0, out_stride=None, out_coff=0):
+    """x 16-bit [N*D,H,W,C] -> y [N*2D,2H,2W,C/4]: trilinear x2 (align_corners=False) of the sum of each 4 consecutive channels."""
+    _dev(x)
+    if x.dtype != y.dtype:
+        raise TypeError("upsample_add3d_fwd: x and y must share one 16-bit dtype")
+    xs, ys = C if in_stride is None else in_stride, C // 4 if out_stride is None else out_stride
+    if x.numel() < N * D * H * W * xs or y.numel() < 8 * N * D * H * W * ys:
+        raise ValueError("upsample_add3d_fwd: tensors smaller than [N*D,H,W,in_stride] / [N*2D,2H,2W,out_stride]")
+    ev = TIMER.start() if TIMER is not None else None
+    _cell3d_call("gs_upsample_add3d_fwd", _p(x), _p(y), N, D, H, W, C, xs, in_coff, ys, out_coff, dt_code(x), _stream())
+    if ev is not None:
+        TIMER.stop("upsample_add3d", ev, 2.0 * N * 8 * D * H * W * (C // 4) * 8 + N * D * H * W * C * 0.75, 2.0 * N * D * H * W * C * 3)
+
+
+def upsample_add3d_bwd(dy, dx, N, D, H, W, C, dy_stride=None, dy_coff=0, dx_stride=None, dx_coff=0):
+    """the exact adjoint: dy 16-bit [N*2D,2H,2W,C/4] -> dx [N*D,H,W,C], the four members of a channel group alike."""
+    _dev(dy)
+    if dy.dtype != dx.dtype:
+        raise TypeError("upsample_add3d_bwd: dy and dx must share one 16-bit dtype")
+    ys, xs = C // 4 if dy_stride is None else dy_stride, C if dx_stride is None else dx_stride
+    if dx.numel() < N * D * H * W * xs or dy.numel() < 8 * N * D * H * W * ys:
+        raise ValueError("upsample_add3d_bwd: tensors smaller than [N*D,H,W,dx_stride] / [N*2D,2H,2W,dy_stride]")
+    ev = TIMER.start() if TIMER is not None else None
+    _cell3d_call("gs_upsample_add3d_bwd", _p(dy), _p(dx), N, D, H, W, C, ys, dy_coff, xs, dx_coff, dt_code(dy), _stream())
+    if ev is not None:
+        TIMER.stop("upsample_add3d", ev, 2.0 * N * D * H * W * (C // 4) * 64, 2.0 * N * D * H * W * C * 3)
