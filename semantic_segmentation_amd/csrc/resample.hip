@@ -16,6 +16,16 @@ struct UpArgs {
     float ry, rx;
 };
 
+// Source coordinate s = o * r, rounded to fp32 ON ITS OWN.  Every kernel derives y0 = int(s) and l = s - y0 from it, and the backward
+// pass is the transpose of the forward only if both see the same l.  Under -ffp-contract=fast the compiler is free to fuse
+// s - y0 into fma(o, r, -y0) in one kernel and not in another (it did so in the backward loops: l off by up to ulp(s) / 2);
+// the empty asm makes the rounded product the only value the subtraction can read.
+__device__ __forceinline__ float src_coord(int o, float r) {
+    float s = (float)o * r;
+    asm volatile("" : "+v"(s));
+    return s;
+}
+
 template <int DT>
 __global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const UpArgs a) {
     const int nch = a.C >> 3;
@@ -26,7 +36,7 @@ __global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const UpArgs a) {
         const int ox = p % a.OW; p /= a.OW;
         const int oy = p % a.OH;
         const int n = p / a.OH;
-        const float sy = oy * a.ry, sx = ox * a.rx;
+        const float sy = src_coord(oy, a.ry), sx = src_coord(ox, a.rx);
         const int y0 = (int)sy, x0 = (int)sx;
         const int y1 = y0 + (y0 < a.IH - 1), x1 = x0 + (x0 < a.IW - 1);
         const float ly = sy - y0, lx = sx - x0;
@@ -57,7 +67,7 @@ __global__ __launch_bounds__(256) void upsample2x_fwd_pair_kernel(const UpArgs a
         const int ox = p % a.OW; p /= a.OW;
         const int oy = p % a.OH;
         const int n = p / a.OH;
-        const float sy = oy * a.ry, sx = ox * a.rx;
+        const float sy = src_coord(oy, a.ry), sx = src_coord(ox, a.rx);
         const int y0 = (int)sy, x0 = (int)sx;
         const int y1 = y0 + (y0 < a.IH - 1), x1 = x0 + (x0 < a.IW - 1);
         const float ly = sy - y0, lx = sx - x0;
@@ -100,13 +110,13 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_kernel(const UpArgs a) {
         for (int i = 0; i < 8; ++i) acc[i] = 0.f;
         for (int oy = oya; oy <= oyb; ++oy) {
             // the same fp32 arithmetic as the forward pass, so forward and backward weights agree exactly
-            const float sy = oy * a.ry;
+            const float sy = src_coord(oy, a.ry);
             const int y0 = (int)sy, y1 = y0 + (y0 < a.IH - 1);
             const float ly = sy - y0;
             const float wy = (y0 == iy ? 1.f - ly : 0.f) + (y1 == iy ? ly : 0.f);
             if (wy == 0.f) continue;
             for (int ox = oxa; ox <= oxb; ++ox) {
-                const float sx = ox * a.rx;
+                const float sx = src_coord(ox, a.rx);
                 const int x0 = (int)sx, x1 = x0 + (x0 < a.IW - 1);
                 const float lx = sx - x0;
                 const float wx = (x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f);
