@@ -977,6 +977,24 @@ int gs_upsample_add3d_fwd(const void* x, void* y, int N, int D, int H, int W, in
 int gs_upsample_add3d_bwd(const void* dy, void* dx, int N, int D, int H, int W, int C, int dy_pix_stride, int dy_coff, int dx_pix_stride,
                           int dx_coff, int dtype, void* stream);
 
+/* Image-side tail of the 3-D Pix2Pix generator (csrc/gen3d.hip; GenSeg-3D/models/networks.py:688-692, the outermost block's
+ * Conv3d(C_in -> C_out, k 3, stride 1, pad 1) + bias + Tanh): x 16-bit dense [N*D,H,W,C_in], C_in a multiple of 8 up to 64; w the
+ * module's fp32 weight [C_out][C_in][3][3][3], C_out 1..4; the image fp32 NCDHW [N,C_out,D,H,W].  Zeros outside the volume; depth
+ * taps never cross a sample.  fp32 accumulation.  Checked before any launch: GS_EINVAL for a null or misaligned pointer (16 bytes
+ * for the 16-bit tensors, 4 for fp32), a bad dtype or dims; GS_EUNSUPPORTED (with an error string that names the limits) for C_in,
+ * C_out or act outside the above.
+ * gs_conv3d_tail_fwd: out = act(conv3d(x, w) + bias); bias may be NULL; act GS_ACT_NONE or GS_ACT_TANH.
+ * gs_conv3d_tail_bwd: du = gscale * dout * (1 - t^2) with t the forward's output (act GS_ACT_NONE: du = gscale * dout, t is not
+ *   read and may be NULL).  dx 16-bit [N*D,H,W,C_in] = the flipped-tap sum over du in fp32, rounded once (overwrites).
+ *   dw [C_out][C_in][3][3][3] = sum du * x and db [C_out] = sum du (fp32, overwrite) through per-part slabs in ws
+ *   (gs_conv3d_tail_bwd_ws_floats floats) added in a fixed order: no atomics, two runs give equal bits.  dx may be NULL; dw and db may
+ *   be NULL together (then x and ws are not read). */
+int gs_conv3d_tail_fwd(const void* x, const float* w, const float* bias, float* out, int N, int D, int H, int W, int Cin, int Cout,
+                       int act, int dtype, void* stream);
+int64_t gs_conv3d_tail_bwd_ws_floats(int N, int D, int H, int W, int Cin, int Cout);
+int gs_conv3d_tail_bwd(const void* x, const float* w, const float* t, const float* dout, void* dx, float* dw, float* db, float* ws,
+                       int N, int D, int H, int W, int Cin, int Cout, int act, float gscale, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

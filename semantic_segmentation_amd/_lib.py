@@ -240,6 +240,9 @@ PROTOTYPES = {
     "gs_cell3d_split_wgrad": (c_int, [_F] * 5 + [c_float] + [_F] * 5 + [c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p]),
     "gs_upsample_add3d_fwd": (c_int, [_P, _P] + [c_int] * 10 + [c_void_p]),
     "gs_upsample_add3d_bwd": (c_int, [_P, _P] + [c_int] * 10 + [c_void_p]),
+    "gs_conv3d_tail_fwd": (c_int, [_P, _F, _F, _F] + [c_int] * 8 + [c_void_p]),
+    "gs_conv3d_tail_bwd_ws_floats": (c_int64, [c_int] * 6),
+    "gs_conv3d_tail_bwd": (c_int, [_P, _F, _F, _F, _P, _F, _F, _F] + [c_int] * 7 + [c_float, c_int, c_void_p]),
 }
 
 _lib = None

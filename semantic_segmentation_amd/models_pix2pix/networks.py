@@ -71,7 +71,23 @@ def init_net(net, init_type='normal', init_gain=0.02, gpu_ids=[]):
 
 
 def define_G(input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, init_type='normal', init_gain=0.02,
-             gpu_ids=[]):
+             gpu_ids=[], upsampling='deconvolution', threed=False):
+    """upsampling / threed (GenSeg-3D/models/networks.py:216-262): threed=True with upsampling='linear' builds the 3-D
+    linear-upsample U-Net (networks3d.UnetGenerator); there 'unet_128' means 6 downs (7 for images, as ever)."""
+    if threed:
+        if upsampling != 'linear' or netG not in ('unet_128', 'unet_256'):
+            raise NotImplementedError("3-D generators on the MI355X hot path: netG 'unet_128' with upsampling='linear' (got netG=%r, "
+                                      "upsampling=%r; the reference's 3-D 'deconvolution' blocks fail to construct)" % (netG, upsampling))
+        if netG == 'unet_256':
+            raise NotImplementedError("3-D 'unet_256' asks for 8 downs, but the reference's conv_arch has 6 rows (a seventh cell raises "
+                                      "IndexError there): use 'unet_128' (6 downs) with upsampling='linear'")
+        from .networks3d import UnetGenerator as UnetGenerator3d
+        net = UnetGenerator3d(input_nc, output_nc, 6, ngf, norm_layer=get_norm_layer(norm_type=norm, threed=True),
+                              upsampling=upsampling, use_dropout=use_dropout)
+        return init_net(net, init_type, init_gain, gpu_ids)
+    if upsampling != 'deconvolution':
+        raise NotImplementedError("2-D generators on the MI355X hot path use upsampling='deconvolution' (got %r); upsampling='linear' "
+                                  "is the 3-D U-Net: threed=True" % upsampling)
     norm_layer = get_norm_layer(norm_type=norm)
     if netG == 'unet_128':
         net = UnetGenerator(input_nc, output_nc, 7, ngf, norm_layer=norm_layer, use_dropout=use_dropout)

@@ -2266,3 +2266,59 @@ def upsample_add3d_bwd(dy, dx, N, D, H, W, C, dy_stride=None, dy_coff=0, dx_stri
     _cell3d_call("gs_upsample_add3d_bwd", _p(dy), _p(dx), N, D, H, W, C, ys, dy_coff, xs, dx_coff, dt_code(dy), _stream())
     if ev is not None:
         TIMER.stop("upsample_add3d", ev, 2.0 * N * D * H * W * (C // 4) * 64, 2.0 * N * D * H * W * C * 3)
+
+
+# ---------------------------------------------------------------------------- 3-D Pix2Pix generator tail (csrc/gen3d.hip)
+# Conv3d(C_in -> C_out, k 3, stride 1, pad 1) + bias + tanh from the 16-bit upsample output to the fp32 NCDHW image.
+def _tail3d_shapes(who, t16, w, img):
+    if img.dim() != 5 or not img.is_contiguous() or img.dtype != torch.float32:
+        raise ValueError(f"{who}: the image must be a contiguous fp32 [N,C_out,D,H,W] tensor")
+    N, Cout, D, H, W = img.shape
+    if t16.dim() != 4 or not t16.is_contiguous() or tuple(t16.shape[:3]) != (N * D, H, W):
+        raise ValueError(f"{who}: the 16-bit tensor must be dense [N*D,H,W,C_in] = [{N * D},{H},{W},C_in], got {tuple(t16.shape)}")
+    Cin = t16.shape[3]
+    if tuple(w.shape) != (Cout, Cin, 3, 3, 3) or not w.is_contiguous():
+        raise ValueError(f"{who}: w must be contiguous [C_out={Cout}, C_in={Cin}, 3, 3, 3], got {tuple(w.shape)}")
+    return N, D, H, W, Cin, Cout
+
+
+def conv3d_tail_fwd(x, w, bias, out, act):
+    """out fp32 [N,C_out,D,H,W] = act(conv3d(x 16-bit [N*D,H,W,C_in], w fp32 [C_out,C_in,3,3,3], stride 1, pad 1) + bias); C_in a
+    multiple of 8 up to 64, C_out 1..4, act ACT_NONE / ACT_TANH."""
+    _dev(x)
+    _f32(w, "w"); _f32(bias, "bias")
+    N, D, H, W, Cin, Cout = _tail3d_shapes("conv3d_tail_fwd", x, w, out)
+    if bias is not None and bias.numel() != Cout:
+        raise ValueError("conv3d_tail_fwd: bias must have C_out entries")
+    ev = TIMER.start() if TIMER is not None else None
+    _cell3d_call("gs_conv3d_tail_fwd", _p(x), _p(w), _p(bias), _p(out), N, D, H, W, Cin, Cout, act, dt_code(x), _stream())
+    if ev is not None:
+        TIMER.stop("conv3d_tail", ev, 2.0 * N * D * H * W * 27 * Cin * Cout, N * D * H * W * (2.0 * Cin + 4.0 * Cout))
+
+
+def conv3d_tail_bwd(x, w, t, dout, dx, dw, db, act, gscale=1.0, ws=None):
+    """du = gscale * dout * (1 - t^2) (act ACT_NONE: gscale * dout; t may be None) -> dx 16-bit [N*D,H,W,C_in] (or None), dw
+    [C_out,C_in,3,3,3] and db [C_out] (fp32, overwritten, deterministic; or both None)."""
+    _f32(w, "w"); _f32(t, "t"); _f32(dw, "dw"); _f32(db, "db"); _f32(ws, "ws")
+    ref = x if x is not None else dx
+    if ref is None:
+        raise ValueError("conv3d_tail_bwd: x or dx must be given")
+    _dev(ref)
+    N, D, H, W, Cin, Cout = _tail3d_shapes("conv3d_tail_bwd", ref, w, dout)
+    if t is not None and (tuple(t.shape) != tuple(dout.shape) or not t.is_contiguous()):
+        raise ValueError("conv3d_tail_bwd: t must be contiguous with dout's shape")
+    if dx is not None and (dx.dtype != ref.dtype or tuple(dx.shape) != tuple(ref.shape) or not dx.is_contiguous()):
+        raise ValueError("conv3d_tail_bwd: dx must be dense [N*D,H,W,C_in] of x's dtype")
+    if dw is not None:
+        if db is None or tuple(dw.shape) != tuple(w.shape) or db.numel() != Cout or not dw.is_contiguous():
+            raise ValueError("conv3d_tail_bwd: dw has w's shape and comes with db [C_out]")
+        need = int(_lib.load().gs_conv3d_tail_bwd_ws_floats(N, D, H, W, Cin, Cout))
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.float32, device=ref.device)
+        elif ws.numel() < need:
+            raise ValueError("conv3d_tail_bwd: ws needs gs_conv3d_tail_bwd_ws_floats floats")
+    ev = TIMER.start() if TIMER is not None else None
+    _cell3d_call("gs_conv3d_tail_bwd", _p(x), _p(w), _p(t), _p(dout), _p(dx), _p(dw), _p(db), _p(ws), N, D, H, W, Cin, Cout, act,
+                 float(gscale), dt_code(ref), _stream())
+    if ev is not None:
+        TIMER.stop("conv3d_tail", ev, 4.0 * N * D * H * W * 27 * Cin * Cout, N * D * H * W * (4.0 * Cin + 8.0 * Cout))
