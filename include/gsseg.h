@@ -881,7 +881,7 @@ int64_t gs_conv_ends_wgrad_ws_floats(int N, int TH, int TW, int Cimg, int C16, i
 int gs_conv_ends_wgrad(const void* t16, const float* img, float* dw, float* db, float* ws, int N, int TH, int TW, int C16, int Cimg,
                        int BH, int BW, int k, int pad, int flip, int w_img_major, float gscale, int dtype, void* stream);
 
-/* The image-side conv of the Pix2Pix networks for Cin = 5..16 image channels (csrc/ends_wide.hip): the PatchGAN's model.0
+/* The image-side conv of the Pix2Pix networks for Cin = 5..16 image channels (csrc/ends_img.hip): the PatchGAN's model.0
  * (models_pix2pix/networks.py:640), the U-Net generator's outermost down-conv (:582) -- both k 4 / stride 2 / pad 1 -- and
  * PixelDiscriminator.net.0 (:686, k 1 / stride 1 / pad 0), between an fp32 NCHW image [N,Cin,IH,IW] and a dense 16-bit NHWC tensor
  * [N,OH,OW,Cout], Cout any multiple of 8 up to 128; w is the module's fp32 weight [Cout][Cin][k][k].  The image is not rounded to 16
@@ -901,7 +901,7 @@ int gs_conv_imgwide_wgrad(const float* x, const void* dy, float* dw, float* ws, 
 int gs_conv_imgwide_dgrad(const void* dy, const float* w, float* dx, int N, int Cin, int IH, int IW, int Cout, int OH, int OW, int k,
                           int stride, int pad, float gscale, int dtype, void* stream);
 
-/* The two ends of the 3-D Pix2Pix discriminators (csrc/ends3d.hip; GenSeg-3D/models/networks.py:806-890 with a 3-D norm layer).  A
+/* The two ends of the 3-D Pix2Pix discriminators (csrc/ends_img.hip, csrc/ends3d.hip; GenSeg-3D/models/networks.py:806-890 with a 3-D norm layer).  A
  * volume is a stack of depth slices: the 16-bit tensors are dense [N*D,H,W,C].
  *
  * Image side -- NLayerDiscriminator.model.0 (GenSeg-3D/models/networks.py:829, Conv3d k 4 / stride 2 / pad 1) and

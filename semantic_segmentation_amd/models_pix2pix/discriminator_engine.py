@@ -14,10 +14,10 @@ added, gradient exact zeros.  Gradients are carried times a power-of-two scale; 
 hooks are those of the generators.
 The two engines supply the facts that differ, as data or short hooks:
   DiscriminatorEngine    images [N,C,H,W], 16-bit tensors [N,H,W,C].  Image side: the direct kernels for 1..4 channels, the fp32-MFMA
-                         kernels of csrc/ends_wide.hip for 5..16 (pix2pix_engine.image_conv_*); stride-2 data gradient: four classes of
+                         kernels of csrc/ends_img.hip for 5..16 (pix2pix_engine.image_conv_*); stride-2 data gradient: four classes of
                          input pixels in one batched launch; head: gs_conv_smallcout_*.
   Discriminator3DEngine  volumes [N,C,D,H,W], which live as a stack of depth slices [N*D,H,W,C] as in unet3d_engine.py.  Image side:
-                         csrc/ends3d.hip gs_conv3d_img_*; middle convs with up to 64 depth-strided taps (ops.geom_conv3d), InstanceNorm3d
+                         csrc/ends_img.hip gs_conv3d_img_*; middle convs with up to 64 depth-strided taps (ops.geom_conv3d), InstanceNorm3d
                          statistics over the WHOLE volume on the [N, OD*OH, OW, C] view; stride-2 data gradient: the eight sub-voxel
                          classes of eight taps in two batched launches of four; head: gs_conv3d_head_* (logits [N,1,OD,OH,OW])."""
 from __future__ import annotations

@@ -14,7 +14,7 @@ Generator (reference models_pix2pix/networks.py:514-617, 8 levels at 256x256):
 Discriminator (:620-665): direct 2->64 conv, three MFMA convs with BN+LeakyReLU, direct 512->1 head (fp32 logits).
 PixelDiscriminator (:668-697) is the same stage list with 1x1 kernels and runs on DiscriminatorEngine(seq="net").
 Images of 5..16 channels (an RGB pair is six; one-hot masks into the generator): the image-side conv, its weight and data gradient
-are the fp32-MFMA kernels of csrc/ends_wide.hip (image_conv_* below) instead of the direct ones; 1..4 channels launch what they did.
+are the fp32-MFMA kernels of csrc/ends_img.hip (image_conv_* below) instead of the direct ones; 1..4 channels launch what they did.
 Gradients are carried multiplied by a power-of-two scale (see unet_engine.py).
 `--norm instance` (InstanceNorm2d without parameters or running statistics, networks.py:23-38): the same plans with the norm's
 statistics per (sample, channel) from gs_in_stats after each normed conv (train and eval alike) and gs_in_act_apply in place of
@@ -56,7 +56,7 @@ def _need_cuda(x):
         raise RuntimeError("semantic_segmentation_amd Pix2Pix networks run on the MI355X only (no CPU / ATen fallback)")
 
 
-IMAGE_NC_MAX = 16           # image channels of the first-layer kernels: 1..4 csrc/direct.hip, 5..16 csrc/ends_wide.hip
+IMAGE_NC_MAX = 16           # image channels of the first-layer kernels: 1..4 csrc/direct.hip, 5..16 csrc/ends_img.hip
 
 
 def _check_image_conv(who, cin, cout):

@@ -1960,80 +1960,76 @@ def maxpool3d_fwd_pair_q8(z_hi, z_lo, z_q8, zq_coff, z_stride, zp_hi, zp_lo, zp_
               zp_stride, NB, D, H, W, C, dt_code(z_hi), _stream())
 
 
-# ---------------------------------------------------------------------------- image-side convs of 5..16 channels (csrc/ends_wide.hip)
-def _imgwide_shapes(who, x_shape, w, t16, k, stride, pad):
-    N, Cin, IH, IW = x_shape
-    if t16.dim() != 4 or not t16.is_contiguous() or t16.shape[0] != N:
-        raise ValueError(f"{who}: the 16-bit tensor must be dense [N,OH,OW,Cout]")
+# ---------------------------------------------------------------------------- image-side convs of images and volumes (csrc/ends_img.hip)
+def _img_shapes(who, x_shape, w, t16, k, stride, pad, rank):
+    """(N, Cin, IH, IW, Cout, OH, OW) of an image (rank 2) or (N, Cin, ID, IH, IW, Cout, OD, OH, OW) of a volume (rank 3), in the order
+    of the C ABI's arguments"""
+    if len(x_shape) != rank + 2:
+        raise ValueError(f"{who}: the {'volume must be [N,Cin,D,H,W]' if rank == 3 else 'image must be [N,Cin,H,W]'}, "
+                         f"got {tuple(x_shape)}")
+    N, Cin, *isz = x_shape
+    od = [conv_out_size(i, k, stride, pad) for i in isz[:-2]]                # [OD] of a volume, [] of an image
+    if t16.dim() != 4 or not t16.is_contiguous() or t16.shape[0] != (N * od[0] if od else N):
+        raise ValueError(f"{who}: the 16-bit tensor must be dense [{'N*OD' if od else 'N'},OH,OW,Cout]")
     _, OH, OW, Cout = t16.shape
-    if tuple(w.shape) != (Cout, Cin, k, k):
-        raise ValueError(f"{who}: w must be [Cout={Cout}, Cin={Cin}, {k}, {k}], got {tuple(w.shape)}")
-    return N, Cin, IH, IW, Cout, OH, OW
+    if tuple(w.shape) != (Cout, Cin) + (k,) * len(isz):
+        raise ValueError(f"{who}: w must be [Cout={Cout}, Cin={Cin}, {', '.join([str(k)] * len(isz))}], got {tuple(w.shape)}")
+    return (N, Cin, *isz, Cout, *od, OH, OW)
 
 
-def _imgwide_call(name, Cin, Cout, k, stride, pad, *args):
+def _call_or_unsupported(name, what, *args):
+    """a C ABI call whose GS_EUNSUPPORTED becomes a NotImplementedError naming what is not covered"""
     rc = getattr(_lib.load(), name)(*args)
     if rc == _lib.GS_EUNSUPPORTED:
-        raise NotImplementedError(f"{name}: Cin={Cin} (5..16), Cout={Cout} (a multiple of 8 up to 128), k/stride/pad={k}/{stride}/{pad} "
-                                  "(4/2/1 or 1/1/0) not covered")
+        raise NotImplementedError(f"{name}: {what} not covered")
     _lib.check(rc, name)
+
+
+def _img_call(name, ptrs, dims, k, stride, pad, *tail):
+    """name(*ptrs, *dims, k, stride, pad, *tail, stream) with dims as _img_shapes returns them"""
+    Cin, Cout = dims[1], dims[len(dims) // 2 + 1]
+    what = (f"Cin={Cin} ({'5..16' if len(dims) == 7 else '1..16'}), Cout={Cout} (a multiple of 8 up to 128), "
+            f"k/stride/pad={k}/{stride}/{pad} (4/2/1 or 1/1/0)")
+    _call_or_unsupported(name, what, *[_p(t) for t in ptrs], *dims, k, stride, pad, *tail, _stream())
+
+
+def _img_wgrad_ws(who, ws, dev, *sizes):
+    """the weight gradient's slab workspace: allocated when ws is None, else checked against gs_<who>_ws_floats(*sizes)"""
+    need = int(getattr(_lib.load(), f"gs_{who}_ws_floats")(*sizes))
+    if ws is None:
+        return torch.empty(need, dtype=torch.float32, device=dev)
+    if ws.numel() < need:
+        raise ValueError(f"{who}: ws needs gs_{who}_ws_floats floats")
+    return ws
 
 
 def conv_imgwide_fwd(x, w, bias, y, k, stride, pad, act=ACT_NONE):
     """y [N,OH,OW,Cout] 16-bit = act(conv(x fp32 [N,Cin,IH,IW], w fp32 [Cout,Cin,k,k]) + bias), Cin 5..16; act ACT_NONE / ACT_LEAKY02."""
     _dev(x)
     _f32(x, "x"); _f32(w, "w"); _f32(bias, "bias")
-    N, Cin, IH, IW, Cout, OH, OW = _imgwide_shapes("conv_imgwide_fwd", x.shape, w, y, k, stride, pad)
-    _imgwide_call("gs_conv_imgwide_fwd", Cin, Cout, k, stride, pad, _p(x), _p(w), _p(bias), _p(y), N, Cin, IH, IW, Cout, OH, OW,
-                  k, stride, pad, act, dt_code(y), _stream())
+    dims = _img_shapes("conv_imgwide_fwd", x.shape, w, y, k, stride, pad, 2)
+    _img_call("gs_conv_imgwide_fwd", (x, w, bias, y), dims, k, stride, pad, act, dt_code(y))
 
 
 def conv_imgwide_wgrad_ws(N, OH, OW, Cin, Cout, k, dev):
-    return torch.empty(int(_lib.load().gs_conv_imgwide_wgrad_ws_floats(N, OH, OW, Cin, Cout, k)), dtype=torch.float32, device=dev)
+    return _img_wgrad_ws("conv_imgwide_wgrad", None, dev, N, OH, OW, Cin, Cout, k)
 
 
 def conv_imgwide_wgrad(x, dy, dw, k, stride, pad, gscale, ws=None):
     """dw fp32 [Cout,Cin,k,k] = gscale * sum dy * x (overwrites; deterministic slab reduction)."""
     _dev(x)
     _f32(x, "x"); _f32(dw, "dw"); _f32(ws, "ws")
-    N, Cin, IH, IW, Cout, OH, OW = _imgwide_shapes("conv_imgwide_wgrad", x.shape, dw, dy, k, stride, pad)
-    if ws is None:
-        ws = conv_imgwide_wgrad_ws(N, OH, OW, Cin, Cout, k, x.device)
-    elif ws.numel() < int(_lib.load().gs_conv_imgwide_wgrad_ws_floats(N, OH, OW, Cin, Cout, k)):
-        raise ValueError("conv_imgwide_wgrad: ws needs gs_conv_imgwide_wgrad_ws_floats floats")
-    _imgwide_call("gs_conv_imgwide_wgrad", Cin, Cout, k, stride, pad, _p(x), _p(dy), _p(dw), _p(ws), N, Cin, IH, IW, Cout, OH, OW,
-                  k, stride, pad, float(gscale), dt_code(dy), _stream())
+    dims = N, Cin, IH, IW, Cout, OH, OW = _img_shapes("conv_imgwide_wgrad", x.shape, dw, dy, k, stride, pad, 2)
+    ws = _img_wgrad_ws("conv_imgwide_wgrad", ws, x.device, N, OH, OW, Cin, Cout, k)
+    _img_call("gs_conv_imgwide_wgrad", (x, dy, dw, ws), dims, k, stride, pad, float(gscale), dt_code(dy))
 
 
 def conv_imgwide_dgrad(dy, w, dx, k, stride, pad, gscale):
     """dx fp32 [N,Cin,IH,IW] = gscale * conv_transpose(dy, w) (overwrites)."""
     _dev(dy)
     _f32(w, "w"); _f32(dx, "dx")
-    N, Cin, IH, IW, Cout, OH, OW = _imgwide_shapes("conv_imgwide_dgrad", dx.shape, w, dy, k, stride, pad)
-    _imgwide_call("gs_conv_imgwide_dgrad", Cin, Cout, k, stride, pad, _p(dy), _p(w), _p(dx), N, Cin, IH, IW, Cout, OH, OW,
-                  k, stride, pad, float(gscale), dt_code(dy), _stream())
-
-
-# ---------------------------------------------------------------------------- the two ends of the 3-D discriminators (csrc/ends3d.hip)
-def _img3d_shapes(who, x_shape, w, t16, k, stride, pad):
-    if len(x_shape) != 5:
-        raise ValueError(f"{who}: the volume must be [N,Cin,D,H,W], got {tuple(x_shape)}")
-    N, Cin, ID, IH, IW = x_shape
-    OD = conv_out_size(ID, k, stride, pad)
-    if t16.dim() != 4 or not t16.is_contiguous() or t16.shape[0] != N * OD:
-        raise ValueError(f"{who}: the 16-bit tensor must be dense [N*OD,OH,OW,Cout]")
-    _, OH, OW, Cout = t16.shape
-    if tuple(w.shape) != (Cout, Cin, k, k, k):
-        raise ValueError(f"{who}: w must be [Cout={Cout}, Cin={Cin}, {k}, {k}, {k}], got {tuple(w.shape)}")
-    return N, Cin, ID, IH, IW, Cout, OD, OH, OW
-
-
-def _img3d_call(name, Cin, Cout, k, stride, pad, *args):
-    rc = getattr(_lib.load(), name)(*args)
-    if rc == _lib.GS_EUNSUPPORTED:
-        raise NotImplementedError(f"{name}: Cin={Cin} (1..16), Cout={Cout} (a multiple of 8 up to 128), k/stride/pad={k}/{stride}/{pad} "
-                                  "(4/2/1 or 1/1/0) not covered")
-    _lib.check(rc, name)
+    dims = _img_shapes("conv_imgwide_dgrad", dx.shape, w, dy, k, stride, pad, 2)
+    _img_call("gs_conv_imgwide_dgrad", (dy, w, dx), dims, k, stride, pad, float(gscale), dt_code(dy))
 
 
 def conv3d_img_fwd(x, w, bias, y, k, stride, pad, act=ACT_NONE):
@@ -2041,37 +2037,32 @@ def conv3d_img_fwd(x, w, bias, y, k, stride, pad, act=ACT_NONE):
     ACT_LEAKY02."""
     _dev(x)
     _f32(x, "x"); _f32(w, "w"); _f32(bias, "bias")
-    N, Cin, ID, IH, IW, Cout, OD, OH, OW = _img3d_shapes("conv3d_img_fwd", x.shape, w, y, k, stride, pad)
-    _img3d_call("gs_conv3d_img_fwd", Cin, Cout, k, stride, pad, _p(x), _p(w), _p(bias), _p(y), N, Cin, ID, IH, IW, Cout, OD, OH, OW,
-                k, stride, pad, act, dt_code(y), _stream())
+    dims = _img_shapes("conv3d_img_fwd", x.shape, w, y, k, stride, pad, 3)
+    _img_call("gs_conv3d_img_fwd", (x, w, bias, y), dims, k, stride, pad, act, dt_code(y))
 
 
 def conv3d_img_wgrad_ws(N, OD, OH, OW, Cin, Cout, k, dev):
-    return torch.empty(int(_lib.load().gs_conv3d_img_wgrad_ws_floats(N, OD, OH, OW, Cin, Cout, k)), dtype=torch.float32, device=dev)
+    return _img_wgrad_ws("conv3d_img_wgrad", None, dev, N, OD, OH, OW, Cin, Cout, k)
 
 
 def conv3d_img_wgrad(x, dy, dw, k, stride, pad, gscale, ws=None):
     """dw fp32 [Cout,Cin,k,k,k] = gscale * sum dy * x (overwrites; deterministic slab reduction)."""
     _dev(x)
     _f32(x, "x"); _f32(dw, "dw"); _f32(ws, "ws")
-    N, Cin, ID, IH, IW, Cout, OD, OH, OW = _img3d_shapes("conv3d_img_wgrad", x.shape, dw, dy, k, stride, pad)
-    if ws is None:
-        ws = conv3d_img_wgrad_ws(N, OD, OH, OW, Cin, Cout, k, x.device)
-    elif ws.numel() < int(_lib.load().gs_conv3d_img_wgrad_ws_floats(N, OD, OH, OW, Cin, Cout, k)):
-        raise ValueError("conv3d_img_wgrad: ws needs gs_conv3d_img_wgrad_ws_floats floats")
-    _img3d_call("gs_conv3d_img_wgrad", Cin, Cout, k, stride, pad, _p(x), _p(dy), _p(dw), _p(ws), N, Cin, ID, IH, IW, Cout, OD, OH, OW,
-                k, stride, pad, float(gscale), dt_code(dy), _stream())
+    dims = N, Cin, ID, IH, IW, Cout, OD, OH, OW = _img_shapes("conv3d_img_wgrad", x.shape, dw, dy, k, stride, pad, 3)
+    ws = _img_wgrad_ws("conv3d_img_wgrad", ws, x.device, N, OD, OH, OW, Cin, Cout, k)
+    _img_call("gs_conv3d_img_wgrad", (x, dy, dw, ws), dims, k, stride, pad, float(gscale), dt_code(dy))
 
 
 def conv3d_img_dgrad(dy, w, dx, k, stride, pad, gscale):
     """dx fp32 [N,Cin,D,H,W] = gscale * conv_transpose3d(dy, w) (overwrites)."""
     _dev(dy)
     _f32(w, "w"); _f32(dx, "dx")
-    N, Cin, ID, IH, IW, Cout, OD, OH, OW = _img3d_shapes("conv3d_img_dgrad", dx.shape, w, dy, k, stride, pad)
-    _img3d_call("gs_conv3d_img_dgrad", Cin, Cout, k, stride, pad, _p(dy), _p(w), _p(dx), N, Cin, ID, IH, IW, Cout, OD, OH, OW,
-                k, stride, pad, float(gscale), dt_code(dy), _stream())
+    dims = _img_shapes("conv3d_img_dgrad", dx.shape, w, dy, k, stride, pad, 3)
+    _img_call("gs_conv3d_img_dgrad", (dy, w, dx), dims, k, stride, pad, float(gscale), dt_code(dy))
 
 
+# ---------------------------------------------------------------------------- one-channel head of the 3-D discriminators (csrc/ends3d.hip)
 def _head3d_shapes(who, t16, w, l, k, pad):
     if l.dim() != 5 or l.shape[1] != 1 or not l.is_contiguous():
         raise ValueError(f"{who}: the logits must be contiguous [N,1,OD,OH,OW]")
@@ -2086,10 +2077,7 @@ def _head3d_shapes(who, t16, w, l, k, pad):
 
 
 def _head3d_call(name, Cin, k, pad, *args):
-    rc = getattr(_lib.load(), name)(*args)
-    if rc == _lib.GS_EUNSUPPORTED:
-        raise NotImplementedError(f"{name}: Cin={Cin} (a multiple of 8 up to 1024), k/pad={k}/{pad} (4/1 or 1/0) not covered")
-    _lib.check(rc, name)
+    _call_or_unsupported(name, f"Cin={Cin} (a multiple of 8 up to 1024), k/pad={k}/{pad} (4/1 or 1/0)", *args)
 
 
 def conv3d_head_fwd(x, w, bias, y, k, pad):

@@ -1,6 +1,6 @@
 """Case lists and exact references for the kernels of the 3-D Pix2Pix discriminators (GenSeg-3D/models/networks.py:806-890 with a 3-D
-norm layer): the image-side conv and the one-channel head of csrc/ends3d.hip (gs_conv3d_img_fwd / _wgrad / _dgrad, gs_conv3d_head_fwd /
-_bwd) and the middle convs on the generic engine through ops.geom_conv3d / geom_conv3d_dgrad_s1 / geom_conv3d_s2_dgrad_class -- on
+norm layer): the image-side conv of csrc/ends_img.hip (gs_conv3d_img_fwd / _wgrad / _dgrad), the one-channel head of csrc/ends3d.hip
+(gs_conv3d_head_fwd / _bwd) and the middle convs on the generic engine through ops.geom_conv3d / geom_conv3d_dgrad_s1 / geom_conv3d_s2_dgrad_class -- on
 tests/exact_reference.py's construction: integer operands whose fp32 sums are exact in any order, so a kernel has to give the one
 correctly rounded value.  Shared by tests/test_disc3d_kernels_gpu.py (kernel against reference, zero tolerance) and
 tests/test_disc3d_reference_cpu.py (every case meets its conditions; the references equal autograd; the stated wrong implementations

@@ -1,4 +1,4 @@
-"""Case lists and exact references for the image-side conv of 5..16 channels (csrc/ends_wide.hip: gs_conv_imgwide_fwd / _wgrad /
+"""Case lists and exact references for the image-side conv of 5..16 channels (csrc/ends_img.hip: gs_conv_imgwide_fwd / _wgrad /
 _dgrad), on tests/exact_reference.py's construction: integer operands whose fp32 sums are exact in any order, so the kernels have
 to give the one correctly rounded value.  Shared by tests/test_disc_wide_kernels_gpu.py (kernel against reference, zero tolerance)
 and tests/test_disc_wide_reference_cpu.py (every case meets its conditions; the stated wrong implementations do not pass)."""

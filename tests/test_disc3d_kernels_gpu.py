@@ -1,7 +1,7 @@
 """The kernels of the 3-D Pix2Pix discriminators at ZERO tolerance on integer operands (tests/disc3d_reference.py), f16 and bf16: the
-image-side conv and the one-channel head of csrc/ends3d.hip, and the k4 middle convs on the generic engine through the 3-D geometry
-builders (64 depth-strided taps in one launch).  Equal after one correct rounding of a 16-bit store; two runs bit-equal; the refusals
-return before any launch (GPU only)."""
+image-side conv of csrc/ends_img.hip, the one-channel head of csrc/ends3d.hip, and the k4 middle convs on the generic engine through
+the 3-D geometry builders (64 depth-strided taps in one launch).  Equal after one correct rounding of a 16-bit store; two runs
+bit-equal; the refusals return before any launch (GPU only)."""
 import pytest
 import torch
 
@@ -278,3 +278,31 @@ def test_refusals_return_before_any_launch():
     with pytest.raises(ValueError, match=r"\[N,Cin,D,H,W\]"):
         ops.conv3d_img_fwd(torch.ones(1, 2, 8, 8, device=dev()), torch.ones(64, 2, 4, 4, 4, device=dev()), None,
                            torch.empty(4, 4, 4, 64, dtype=torch.float16, device=dev()), 4, 2, 1)
+
+
+@pytest.mark.parametrize("dtn,dt", er.DTS)
+@pytest.mark.parametrize("case", [(5, 8, 1, (2, 3, 70)), (16, 128, 3, (3, 4, 5))], ids=lambda c: f"c{c[0]}-o{c[1]}-n{c[2]}")
+def test_k1_volume_equals_k1_image_with_depth_in_rows(case, dtn, dt):
+    """a k1 conv is pointwise and its kernel is rank-free: on random normal operands (summation order shows) conv3d_img_fwd / _wgrad /
+    _dgrad on [N,Cin,D,H,W] give the bits of conv_imgwide_fwd / _wgrad / _dgrad on the same memory viewed as [N,Cin,D*H,W]"""
+    from semantic_segmentation_amd import ops
+    Cin, Cout, N, (D, H, W) = case
+    g = torch.Generator().manual_seed(31 * Cin + Cout)
+    x = torch.randn(N, Cin, D, H, W, generator=g).to(dev())
+    w = torch.randn(Cout, Cin, 1, 1, 1, generator=g).to(dev())
+    b = torch.randn(Cout, generator=g).to(dev())
+    dy = torch.randn(N * D, H, W, Cout, generator=g).to(dt).to(dev())
+    x2, w2, dy2 = x.view(N, Cin, D * H, W), w.view(Cout, Cin, 1, 1), dy.view(N, D * H, W, Cout)
+    y3, y2 = full((N * D, H, W, Cout), dt), full((N, D * H, W, Cout), dt)
+    ops.conv3d_img_fwd(x, w, b, y3, 1, 1, 0, ACT_LEAKY02)
+    ops.conv_imgwide_fwd(x2, w2, b, y2, 1, 1, 0, ACT_LEAKY02)
+    assert torch.equal(y3.view(torch.int16).flatten(), y2.view(torch.int16).flatten()), f"k1 forward {dtn}"
+    g3, g2 = full(w.shape, torch.float32), full(w2.shape, torch.float32)
+    ops.conv3d_img_wgrad(x, dy, g3, 1, 1, 0, d3.GSCALE)
+    ops.conv_imgwide_wgrad(x2, dy2, g2, 1, 1, 0, d3.GSCALE)
+    assert torch.equal(g3.view(torch.int32).flatten(), g2.view(torch.int32).flatten()), f"k1 weight gradient {dtn}"
+    dx3, dx2 = full(x.shape, torch.float32), full(x2.shape, torch.float32)
+    ops.conv3d_img_dgrad(dy, w, dx3, 1, 1, 0, d3.GSCALE)
+    ops.conv_imgwide_dgrad(dy2, w2, dx2, 1, 1, 0, d3.GSCALE)
+    assert torch.equal(dx3.view(torch.int32).flatten(), dx2.view(torch.int32).flatten()), f"k1 data gradient {dtn}"
+    assert bool(torch.isfinite(g3).all()) and bool((g3 != SENT).all()) and bool((dx3 != SENT).all()), "outputs were not written"

@@ -1,4 +1,4 @@
-"""gs_conv_imgwide_fwd / _wgrad / _dgrad (csrc/ends_wide.hip: the image-side conv of 5..16 channels) at ZERO tolerance on integer
+"""gs_conv_imgwide_fwd / _wgrad / _dgrad (csrc/ends_img.hip: the image-side conv of 5..16 channels) at ZERO tolerance on integer
 operands (tests/disc_wide_reference.py), f16 and bf16; two runs bit-equal; the refusals return before any launch (GPU only)."""
 import pytest
 import torch

@@ -1,5 +1,5 @@
-"""The 3-D Pix2Pix discriminators (models_pix2pix/discriminator_engine.py, csrc/ends3d.hip) timed at the reference's --crop_size, 64^3
-(DESIGN.md section 4.5d): forward + backward with dx of NLayerDiscriminator(2, 64, 3) and PixelDiscriminator(2, 64) on volumes, batch 1
+"""The 3-D Pix2Pix discriminators (models_pix2pix/discriminator_engine.py, csrc/ends_img.hip, csrc/ends3d.hip) timed at the reference's
+--crop_size, 64^3: forward + backward with dx of NLayerDiscriminator(2, 64, 3) and PixelDiscriminator(2, 64) on volumes, batch 1
 and 4, under BatchNorm3d and InstanceNorm3d, the two norms interleaved in one process; then every launch of each plan on its own
 (event pairs around each call, in the plan's order): time, algorithmic TFLOP/s for the convs, GB/s for the passes.  The algorithmic
 work is computed here from the shapes: a conv's 2 * outputs * Cin * taps (pad taps included), and the bytes each launch has to

@@ -1,4 +1,4 @@
-"""The image-side conv of 5..16 channels (csrc/ends_wide.hip) and the discriminators that use it, timed:
+"""The image-side conv of 5..16 channels (csrc/ends_img.hip) and the discriminators that use it, timed:
 
   kernels   at 256^2, batch 2 and batch 32, ndf 64: gs_conv_imgwide_fwd / _wgrad / _dgrad at 6 channels beside the direct kernels
             gs_conv_smallcin_fwd / _wgrad / _dgrad at 4 channels on the same shape, interleaved rounds in one process; per kernel
